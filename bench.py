@@ -1,6 +1,6 @@
 """Benchmark: FTRL timesteps/s at d=64, T=1e4 (BASELINE.json metric) on 1..N MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU, RCCL)
 
 `python bench.py --gpus N` with N > 1 and no launcher around it starts the N ranks itself
@@ -21,11 +21,21 @@ data-path collective); each step ends with one all-gather of the regrets to
 collect the regret vector (the only exchange the path has).
 
 Printed (rank 0, one JSON line): value = all ranks' timesteps / max-over-ranks
-time; roofline of the kernel from HIP events on its stream (algorithmic bytes =
-(8d+8) per timestep per pass over z: one pass with the closed-form comparator, two
-with the streamed one); cpu_baseline = oracle/ocx_oracle.c (C port of
-_simulate_alg_core) single-threaded on a bounded sample of the same sequences; the
-parity error of the GPU regrets against that CPU sample.
+time; ms_per_step = that time per timed step; roofline of the kernel from HIP events on
+its stream (algorithmic bytes = (8d+8) per timestep per pass over z: one pass with the
+closed-form comparator, two with the streamed one).
+
+A plain run does only that: generate the batch, warm up, time --steps steps, print.
+``--full`` adds the legs that take runs of their own (null in a plain line): two_pass (the
+two-pass kernel beside the default), end_to_end and end_to_end_pipelined (generation +
+simulation per batch), cpu_baseline = oracle/ocx_oracle.c (C port of _simulate_alg_core)
+single-threaded and on all cores on a bounded sample of the same sequences, and the parity
+error of the GPU regrets against that CPU sample.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller as
+DIR/regret.npy (float64: the B regrets of the rank's batch, or the gathered world * B
+vector of a multi-rank run).  The inputs depend on the arguments alone (base seed 0), so
+two builds run with the same arguments can be compared value for value.
 """
 from __future__ import annotations
 
@@ -64,15 +74,22 @@ def parse():
                     help="closed: comparator loss T/2 - ||theta_T|| where the kernel certifies "
                          "it (one pass over z; not in exact lanes mode); two-pass: the "
                          "reference's second streaming pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the two-pass kernel, "
+                         "end to end with generation (sequential and pipelined), the CPU "
+                         "baselines and the parity check against them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the regrets the last timed step "
+                         "computed as DIR/regret.npy (float64)")
     ap.add_argument("--two-pass-steps", type=int, default=3,
-                    help="launches of the two-pass kernel timed after the metric for the "
-                         "two_pass comparison (0 disables; profile runs use 0 so every "
+                    help="(--full) launches of the two-pass kernel timed after the metric for "
+                         "the two_pass comparison (0 disables; profile runs use 0 so every "
                          "ocx_alg_kernel launch in the trace is the default one)")
     ap.add_argument("--e2e-steps", type=int, default=10,
-                    help="untimed-for-the-metric batches of generation + simulation reported "
-                         "as end_to_end (0 disables)")
+                    help="(--full) untimed-for-the-metric batches of generation + simulation "
+                         "reported as end_to_end (0 disables)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="budget of the CPU-baseline sample (0 disables)")
+                    help="(--full) budget of the CPU-baseline sample (0 disables)")
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (= RCCL over xGMI, one GPU per rank) or gloo (rehearsal: ranks may "
                          "share a GPU, the regret gather goes through host memory)")
@@ -408,6 +425,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kern_ms = float(np.mean([s.elapsed_time(e) for s, e in ev]))
+    if a.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, before any --full leg runs
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        last = gathered if dist_on else db.regret[:B]
+        np.save(os.path.join(a.dump_outputs, "regret.npy"),
+                last.cpu().numpy().astype(np.float64, copy=False))
     # sequences in waves that streamed the second pass (a wave holds S sequences)
     fl = np.ones(db.L.G * db.L.S, dtype=np.int32)
     fl[:B] = flags.cpu().numpy() if closed else 0
@@ -416,7 +439,7 @@ def main():
 
     # the same kernel with the reference's second streaming pass, for comparison
     two_pass = None
-    if closed and a.two_pass_steps > 0:
+    if a.full and closed and a.two_pass_steps > 0:
         ev2 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                for _ in range(a.two_pass_steps + 1)]
         for s2, e2 in ev2:
@@ -435,7 +458,7 @@ def main():
     # End to end (outside the metric's timed region): regenerate the batch on device and
     # simulate it, a.e2e_steps times — what a g(T) sweep / configs[2] job does per batch.
     e2e = None
-    if a.e2e_steps > 0:
+    if a.full and a.e2e_steps > 0:
         eg = [[torch.cuda.Event(enable_timing=True) for _ in range(3)]
               for _ in range(a.e2e_steps)]
         if dist_on:
@@ -470,7 +493,7 @@ def main():
     # worth of runs (run0 + k*B) in one call, generation of one sub-batch beside the FTRL pass
     # over the previous one; checked bit for bit against the same call run sequentially
     e2e_pipe = None
-    if a.e2e_steps > 0:
+    if a.full and a.e2e_steps > 0:
         gp = torch.zeros(1, dtype=torch.float64, device=dev)
         gs = torch.zeros(1, dtype=torch.float64, device=dev)
         db.generate_simulate(0, run0, 1, gmax=gp)  # warm (events, streams)
@@ -531,7 +554,7 @@ def main():
         except (OSError, ValueError):
             pass
         cpu, parity = None, None
-        if a.cpu_seconds > 0:  # rank 0, every world size, after the timed region
+        if a.full and a.cpu_seconds > 0:  # rank 0, every world size, after the timed region
             cpu, parity = cpu_leg(a, T, d, B, regrets)
         out = {
             "metric": "FTRL timesteps/sec (whole node) at d=64, T=1e4; max |regret-ref| error",

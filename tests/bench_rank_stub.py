@@ -27,7 +27,7 @@ def main():
     dist.all_gather_object(rows, {"rank": rank, "local_rank": local, "gpu": gpu,
                                   "pid": os.getpid(), "dist_on": dist_on})
     cpu = parity = None
-    if rank == 0 and a.cpu_seconds > 0:
+    if rank == 0 and a.full and a.cpu_seconds > 0:
         from oracle import oracle as O
         regrets = np.array([O.simulate_alg(*O.gT_sample(0, a.T, r, a.d), 0, math.sqrt(2))
                             for r in range(a.B)])

@@ -24,7 +24,7 @@ def _env(**kw):
 def test_launcher_spawns_two_gloo_ranks():
     code = ("import sys; sys.path.insert(0, %r); import bench; "
             "sys.exit(bench.launch_ranks(2, ['--gpus', '2', '--dist-backend', 'gloo', "
-            "'--B', '6', '--T', '200', '--d', '8', '--cpu-seconds', '0.2'], "
+            "'--B', '6', '--T', '200', '--d', '8', '--full', '--cpu-seconds', '0.2'], "
             "script=%r))" % (ROOT, STUB))
     p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True,
                        timeout=180, env=_env())

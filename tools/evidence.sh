@@ -8,7 +8,7 @@
 # than failing tests (pytest exit 1), so a crash, abort or time limit is never followed by
 # more GPU work.  Steps:
 #   suite        pytest -m gpu (one process) and smoke()
-#   bench        the default bench line (python bench.py)
+#   bench        the bench line with every leg (python bench.py --full)
 #   stats        rocprofv3 --kernel-trace --stats of a 20-step bench run (kernel averages)
 #   traffic      two PMC passes (FETCH_SIZE, WRITE_SIZE) over a 2-step bench run, reduced by
 #                tools/pmc_traffic.py (gfx950 x2 read correction) into TAG_traffic.json
@@ -56,14 +56,14 @@ for step in "$@"; do
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "${O}_smoke.log" 2>&1 || fail smoke $?
     tail -1 "${O}_smoke.log" ;;
   bench)
-    timeout -k 10 600 python bench.py > "${O}_bench.log" 2>&1 || fail bench $?
+    timeout -k 10 600 python bench.py --full > "${O}_bench.log" 2>&1 || fail bench $?
     grep '^{' "${O}_bench.log" > "${O}_bench.json"; cut -c1-300 "${O}_bench.json" ;;
   stats)
-    (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "${O}_stats" -o s --output-format csv -- python3 "$R/bench.py" --steps 20 --warmup 3 --cpu-seconds 0 --two-pass-steps 0 > "${O}_stats.log" 2>&1) || fail stats $?
+    (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "${O}_stats" -o s --output-format csv -- python3 "$R/bench.py" --full --steps 20 --warmup 3 --cpu-seconds 0 --two-pass-steps 0 > "${O}_stats.log" 2>&1) || fail stats $?
     head -6 "${O}_stats/s_kernel_stats.csv" | cut -c1-160 ;;
   traffic)
     for C in FETCH_SIZE WRITE_SIZE; do
-      (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --pmc $C --output-format csv -d "${O}_pmc_$C" -o pmc -- python3 "$R/bench.py" --steps 2 --warmup 0 --cpu-seconds 0 --two-pass-steps 0 --e2e-steps 1 > "${O}_pmc_$C.log" 2>&1) || fail "pmc $C" $?
+      (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --pmc $C --output-format csv -d "${O}_pmc_$C" -o pmc -- python3 "$R/bench.py" --full --steps 2 --warmup 0 --cpu-seconds 0 --two-pass-steps 0 --e2e-steps 1 > "${O}_pmc_$C.log" 2>&1) || fail "pmc $C" $?
     done
     python tools/pmc_traffic.py --fetch "${O}_pmc_FETCH_SIZE" --write "${O}_pmc_WRITE_SIZE" --kernel "ocx_alg_pipe_kernel<8, 8, 9," --label ocx_alg_pipe_kernel --B 32768 --T 10000 --d 64 --P 8 --passes 1 --out "${O}_traffic.json" > /dev/null || fail traffic $?
     head -c 600 "${O}_traffic.json"; echo ;;
