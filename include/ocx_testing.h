@@ -30,10 +30,24 @@ int ocx_test_gT_regrets_unclean(uint64_t base_seed, int64_t T, int64_t run0, int
  * between them, closed-form comparator.  regret [B] (device): bit-identical to one launch
  * for every sequence the closed form certifies; NaN for the others, and *bad (device int,
  * zeroed by the caller) set to 1.  Synchronises `stream`.  Butterfly layouts the pipelined
- * kernel takes (P in {8, 16, 32}, C in {4, 8, 16, 32}). */
+ * kernel takes (P in {8, 16, 32}, C in {4, 8, 16, 32}, and P = 64 with C = 16); any other
+ * layout is OCX_E_UNSUPPORTED. */
 int ocx_test_alg_pipe_chunked(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
                               double eta0, int64_t chunk_steps, double* regret, int* bad,
                               void* stream);
+
+/* The sub-batch pipeline's FTRL launch on a resident batch: FTRL over wave-groups
+ * [g0, g0 + gn) of the layout (group g holds sequences g*S .. g*S + S - 1), dispatched as the
+ * pipeline dispatches it — the pipelined kernel's lean whole-run form where the pipelined
+ * kernel takes the layout (8 x 8, 16 x 4, 8 x 4), the plain kernel over a group range otherwise
+ * (8 x 2); any other layout is OCX_E_UNSUPPORTED.  onepass: 0 the streamed second pass, 1 the
+ * closed-form comparator where the kernel certifies it.  regret [B] (device): written for the
+ * range's sequences only.  gmax (device, nullable; one 64-bit word the caller initialises,
+ * 0 for a fresh maximum): max-folded with the bit pattern of every positive regret of the
+ * range, so from 0 it ends as the double max(0.0, max regret).  Synchronises `stream`. */
+int ocx_test_alg_range(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                       double eta0, int onepass, int64_t g0, int64_t gn, double* regret,
+                       double* gmax, void* stream);
 
 /* Batches that have entered the trailing pipeline (ocx_run_gen_sim_trailing) in this process
  * so far: lets a test assert that a call took that path rather than the sequential loop. */

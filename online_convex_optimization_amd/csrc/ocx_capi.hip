@@ -1284,6 +1284,31 @@ int ocx_test_alg_pipe_chunked(const ocx_layout* L, const double* z_tiled, const 
     return OCX_OK;
 }
 
+int ocx_test_alg_range(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                       double eta0, int onepass, int64_t g0, int64_t gn, double* regret,
+                       double* gmax, void* stream) {
+    StreamDevice sd_(stream);
+    if (int rc = check_layout(L)) return rc;
+    // the sub-batch pipeline's FTRL launch (ocx_run_gen_sim_pipelined), on the layouts it runs
+    const bool pipe = ocx_pipe_supported(L);
+    if (pipe ? !ocx_pipe_lean_launchable(L) : !(!L->chain && L->P == 8 && L->C == 2))
+        return fail(OCX_E_UNSUPPORTED, "not a layout of the pipelines' FTRL range forms");
+    if (onepass != 0 && onepass != 1) return fail(OCX_E_INVALID, "onepass must be 0 or 1");
+    if (g0 < 0 || gn < 0 || g0 + gn > L->G) return fail(OCX_E_INVALID, "group range outside the layout");
+    if (gn > 0 && (!regret || (L->z_elems && (!z_tiled || !y_tiled))))
+        return fail(OCX_E_INVALID, "NULL buffer");
+    const hipStream_t st = (hipStream_t)stream;
+    unsigned long long* gm = reinterpret_cast<unsigned long long*>(gmax);
+    const hipError_t e = pipe ? ocx_launch_alg_pipe_lean(L, z_tiled, y_tiled, eta0, regret, onepass,
+                                                         g0, gn, gm, st)
+                              : ocx_launch_alg_range(L, z_tiled, y_tiled, eta0, regret, onepass, g0,
+                                                     gn, gm, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    OCX_HIP(e);
+    OCX_HIP(es);
+    return OCX_OK;
+}
+
 int64_t ocx_test_trailing_batches(void) { return ocx_trailing_batches_run(); }
 
 int ocx_test_gT_regrets_unclean(uint64_t base_seed, int64_t T, int64_t run0, int64_t R,

@@ -167,3 +167,24 @@ def test_gen_simulate_rejects_bad_arguments_before_the_gpu():
         msg = ctypes.create_string_buffer(256)
         lib.ocx_last_error(msg, 256)
         assert msg.value, (run0, nbatch, flags)
+
+
+def test_alg_range_rejects_bad_arguments_before_the_gpu():
+    """ocx_test_alg_range takes the layouts the sub-batch pipeline's FTRL launch runs (8 x 8,
+    16 x 4, 8 x 4, 8 x 2) and group ranges inside the layout; everything else is reported
+    through the error channel before a device is touched."""
+    import ctypes
+    lib = _lib.load()
+    buf = ctypes.c_void_p(16)  # never dereferenced: the checks come first
+
+    def rc(L, onepass, g0, gn, reg=buf):
+        return lib.ocx_test_alg_range(ctypes.byref(L), buf, buf, 1.0, onepass, g0, gn, reg, None,
+                                      None)
+
+    for d, P in ((64, 32), (128, 8), (64, -8), (16, 4), (16, -8), (1024, 64)):
+        assert rc(_lib.layout(37, 10, d, P), 1, 0, 1) == -3, (d, P)
+    for d, P in ((64, 8), (64, 16), (32, 8), (16, 8)):
+        L = _lib.layout(37, 10, d, P)
+        assert rc(L, 1, -1, 1) == -1 and rc(L, 1, 0, L.G + 1) == -1 and rc(L, 1, L.G, 1) == -1
+        assert rc(L, 1, 0, -1) == -1 and rc(L, 2, 0, 1) == -1 and rc(L, 0, 0, 1, None) == -1
+        assert _lib.last_error()
