@@ -55,6 +55,9 @@
  * 0.3.0 adds the general exact-FTL solver (ocx_exact_ball_solve, ocx_dev_exact_ball_solve,
  * ocx_dev_exact_ball_solve_tiled); nothing existing changed.  0.4.0 adds
  * ocx_dev_gen_simulate (generation overlapped with FTRL); nothing existing changed.
+ * The regret-curve symbols (ocx_curve_workspace_bytes, ocx_dev_simulate_alg_curve,
+ * ocx_simulate_alg_curve_batch) were added without a version change: the number stays 400 and
+ * nothing existing changed; a caller that needs them looks the symbols up.
  *
  * Checking the ABI: one intermediate 0.1.x tree exported ocx_ftrl_vs_exact_batch WITH a
  * `norm` argument under the same symbol and the same version number as the release without
@@ -335,6 +338,51 @@ int ocx_dev_simulate_alg_ex(const ocx_layout* L, const double* z_tiled, const do
                             int alg_flag, double eta0, const double* comparator, double* regret,
                             double* cum_loss, double* comp_loss, double* x_last, int flags,
                             int32_t* closed_out, void* stream);
+
+/* Regret curves: fast_algorithms.py:88-115 observed at K checkpoint horizons in one pass.
+ * FTRL and FTL are online, so the first t steps of a run on (z, y) are the run on
+ * (z[:t], y[:t]): for checkpoints 0 <= t_1 < ... < t_K <= T (strictly increasing; 0 and T
+ * allowed) and sequence b,
+ *   regret[b][k], cum_loss[b][k], comp_loss[b][k]
+ *       == simulate_alg on (z[b][:t_k], y[b][:t_k], alg_flag, eta0)
+ * (cum_loss: the loss paid in steps 0 .. t_k - 1; comp_loss: the loss of FTL(theta_{t_k}) over
+ * those t_k rows, fast_algorithms.py:113-115 on the prefix; t_k = 0 gives zeros), with the bits
+ * ocx_dev_simulate_alg_ex gives on the truncated input in the same layout and with the same
+ * flags.  alg_flag 0 = FTRL, else FTL; no caller comparator.
+ *
+ * bytes of caller-owned device workspace for K checkpoints in layout L
+ * (0 for K == 0; negative ocx_status on error) */
+int64_t ocx_curve_workspace_bytes(const ocx_layout* L, int64_t K);
+
+/* device: checkpoints is a DEVICE int64 array [K], strictly increasing in [0, L->T] — a
+ * precondition the call cannot see: an array that breaks it gives meaningless numbers, but
+ * the kernels never leave the batch, the outputs and the workspace whatever it holds;
+ * regret / cum_loss / comp_loss: device [B][K] row-major, each nullable;
+ * closed_out [B][K] int32 nullable (1 = closed form taken);
+ * flags: 0, or OCX_ALG_CLOSED_COMPARATOR / OCX_ALG_CLIPPED_ROWS (one request, as in
+ * ocx_dev_simulate_alg_ex: the kernel certifies rows and sub-gradients itself, per prefix;
+ * a pair (b, k) it cannot certify gets the streamed pass over its prefix, bit-identical to
+ * flags 0, and a certified sequence keeps the closed form whatever shares its wave);
+ * workspace: workspace_bytes >= ocx_curve_workspace_bytes(L, K) of device memory, 8-byte
+ * aligned, the call's own until the stream has passed it;
+ * K == 0, B == 0 and T == 0 are valid and launch nothing or next to nothing;
+ * asynchronous, no allocation, no sync: capture-safe like the other dev entry points.
+ * Cost: one read of z when every prefix is certified; otherwise the prefixes of the
+ * uncertified pairs are read once more (at most sum_k t_k rows per sequence). */
+int ocx_dev_simulate_alg_curve(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                               int alg_flag, double eta0, const int64_t* checkpoints, int64_t K,
+                               double* regret, double* cum_loss, double* comp_loss,
+                               int32_t* closed_out, int flags, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
+/* host: numpy buffers in, [B][K] out; checkpoints is a HOST array, validated here (order,
+ * range, K >= 0) before any device is touched.
+ * Bit-exact layouts (lanes_per_seq 1 / -k): streamed comparator for every pair;
+ * other modes: closed form where certified. */
+int ocx_simulate_alg_curve_batch(const double* z, const double* y, int64_t B, int64_t T, int64_t d,
+                                 int alg_flag, double eta0, const int64_t* checkpoints, int64_t K,
+                                 double* regret, double* cum_loss, double* comp_loss,
+                                 int32_t* closed_out, int lanes_per_seq, int device);
 
 /* ocx_ftl_exact_batch on device (`norm` 0 l2, 1 l1, 2 linf). */
 int ocx_dev_ftl_exact(const ocx_layout* L, const double* z_tiled, const double* y_tiled, int norm,

@@ -390,6 +390,42 @@ int ocx_dev_simulate_alg_ex(const ocx_layout* L, const double* z_tiled, const do
     return OCX_OK;
 }
 
+int64_t ocx_curve_workspace_bytes(const ocx_layout* L, int64_t K) {
+    if (int rc = check_layout(L)) return rc;
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    if (L->B < 0 || L->T < 0 || L->G != ceil_div(L->B, L->S))
+        return fail(OCX_E_INVALID, "corrupt layout");
+    // strictly increasing checkpoints in [0, T]: at most T + 1 of them (bounds the product)
+    if (K > L->T + 1) return fail(OCX_E_INVALID, "more checkpoints than horizons 0..T");
+    return ocx_curve_ws_bytes(L, K);
+}
+
+int ocx_dev_simulate_alg_curve(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                               int alg_flag, double eta0, const int64_t* checkpoints, int64_t K,
+                               double* regret, double* cum_loss, double* comp_loss,
+                               int32_t* closed_out, int flags, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    StreamDevice sd_(stream);
+    const int64_t need = ocx_curve_workspace_bytes(L, K);  // checks the layout and K
+    if (need < 0) return (int)need;
+    if (flags & ~(OCX_ALG_CLIPPED_ROWS | OCX_ALG_CLOSED_COMPARATOR))
+        return fail(OCX_E_INVALID, "unknown flags");
+    if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL input buffer");
+    if (K > 0 && !checkpoints) return fail(OCX_E_INVALID, "NULL checkpoints");
+    if (need > 0 && (!workspace || workspace_bytes < (size_t)need))
+        return fail(OCX_E_INVALID, "workspace smaller than ocx_curve_workspace_bytes(L, K) = " +
+                                       std::to_string(need));
+    if (need > 0 && (reinterpret_cast<uintptr_t>(workspace) & 7) != 0)
+        return fail(OCX_E_INVALID, "workspace is not 8-byte aligned");
+    if (K == 0 || L->B == 0) return OCX_OK;
+    // the two flags are one request: the kernel certifies every row and sub-gradient itself
+    OCX_HIP(ocx_launch_alg_curve(L, z_tiled, y_tiled, alg_flag != 0 ? 1 : 0, eta0, checkpoints, K,
+                                 regret, cum_loss, comp_loss, closed_out,
+                                 (flags & (OCX_ALG_CLIPPED_ROWS | OCX_ALG_CLOSED_COMPARATOR)) ? 1 : 0,
+                                 workspace, (hipStream_t)stream));
+    return OCX_OK;
+}
+
 int ocx_dev_ftl_exact(const ocx_layout* L, const double* z_tiled, const double* y_tiled, int norm,
                       double* cum_loss, double* comp_loss, double* cmp_action, int32_t* regime,
                       void* stream) {
@@ -604,6 +640,60 @@ int ocx_simulate_alg_batch(const double* z, const double* y, int64_t B, int64_t 
     if (cum_loss) std::memcpy(cum_loss, h.data() + B, B * 8);
     if (comp_loss) std::memcpy(comp_loss, h.data() + 2 * B, B * 8);
     if (x_last && d) std::memcpy(x_last, h.data() + 3 * B, (size_t)B * d * 8);
+    return OCX_OK;
+}
+
+int ocx_simulate_alg_curve_batch(const double* z, const double* y, int64_t B, int64_t T, int64_t d,
+                                 int alg_flag, double eta0, const int64_t* checkpoints, int64_t K,
+                                 double* regret, double* cum_loss, double* comp_loss,
+                                 int32_t* closed_out, int lanes_per_seq, int device) {
+    ocx_layout L;
+    if (int rc = ocx_layout_init(B, T, d, lanes_per_seq, &L)) return rc;
+    // everything about the checkpoints before any device or data pointer is touched
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    if (K > 0 && !checkpoints) return fail(OCX_E_INVALID, "NULL checkpoints");
+    for (int64_t k = 0; k < K; ++k) {
+        if (checkpoints[k] < 0 || checkpoints[k] > T)
+            return fail(OCX_E_INVALID, "checkpoint " + std::to_string(checkpoints[k]) +
+                                           " outside [0, T = " + std::to_string(T) + "]");
+        if (k > 0 && checkpoints[k] <= checkpoints[k - 1])
+            return fail(OCX_E_INVALID, "checkpoints must be strictly increasing");
+    }
+    if (B == 0 || K == 0) return OCX_OK;
+    if ((T * d > 0 && !z) || (T > 0 && !y)) return fail(OCX_E_INVALID, "NULL z/y");
+    const int64_t wsb = ocx_curve_workspace_bytes(&L, K);
+    if (wsb < 0) return (int)wsb;
+    DevCtx* cx;
+    if (int rc = ctx_enter(device, &cx)) return rc;
+    std::lock_guard<std::mutex> lk(cx->mu);
+    hipStream_t st = cx->stream;
+    const size_t nz = (size_t)(B * T * d), ny = (size_t)(B * T), nk = (size_t)(B * K);
+    OCX_HIP(cx->zraw.ensure(nz * 8));
+    OCX_HIP(cx->yraw.ensure(ny * 8));
+    OCX_HIP(cx->zt.ensure((size_t)L.z_elems * 8));
+    OCX_HIP(cx->yt.ensure((size_t)L.y_elems * 8));
+    OCX_HIP(cx->out.ensure(nk * (3 * 8 + 4)));
+    OCX_HIP(cx->sw.ensure((size_t)K * 8));
+    OCX_HIP(cx->theta.ensure((size_t)wsb));
+    if (nz) OCX_HIP(hipMemcpyAsync(cx->zraw.p, z, nz * 8, hipMemcpyHostToDevice, st));
+    if (ny) OCX_HIP(hipMemcpyAsync(cx->yraw.p, y, ny * 8, hipMemcpyHostToDevice, st));
+    OCX_HIP(hipMemcpyAsync(cx->sw.p, checkpoints, (size_t)K * 8, hipMemcpyHostToDevice, st));
+    OCX_HIP(ocx_launch_pack(&L, cx->zraw.as<double>(), cx->yraw.as<double>(), cx->zt.as<double>(),
+                            cx->yt.as<double>(), st));
+    double* o = cx->out.as<double>();
+    int32_t* oc = reinterpret_cast<int32_t*>(o + 3 * nk);
+    // bit-exact modes keep the reference's streamed comparator sum for every pair
+    const int onepass = (lanes_per_seq == 1 || lanes_per_seq < 0) ? 0 : 1;
+    OCX_HIP(ocx_launch_alg_curve(&L, cx->zt.as<double>(), cx->yt.as<double>(),
+                                 alg_flag != 0 ? 1 : 0, eta0, cx->sw.as<int64_t>(), K, o, o + nk,
+                                 o + 2 * nk, oc, onepass, cx->theta.p, st));
+    std::vector<double> h(3 * nk + (nk + 1) / 2);
+    OCX_HIP(hipMemcpyAsync(h.data(), o, nk * (3 * 8 + 4), hipMemcpyDeviceToHost, st));
+    OCX_HIP(hipStreamSynchronize(st));
+    if (regret) std::memcpy(regret, h.data(), nk * 8);
+    if (cum_loss) std::memcpy(cum_loss, h.data() + nk, nk * 8);
+    if (comp_loss) std::memcpy(comp_loss, h.data() + 2 * nk, nk * 8);
+    if (closed_out) std::memcpy(closed_out, h.data() + 3 * nk, nk * 4);
     return OCX_OK;
 }
 

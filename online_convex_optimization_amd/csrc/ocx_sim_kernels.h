@@ -19,6 +19,16 @@ bool ocx_pipe_supported(const ocx_layout* L);
 hipError_t ocx_launch_alg_pipe(const ocx_layout* L, const double* zt, const double* yt, int ftl,
                                double eta0, double* reg, double* cum, double* comp,
                                int* closed_out, int onepass, hipStream_t st);
+// Regret curves (ocx_alg_curve.hip): FTRL / FTL observed at the K checkpoints ck (device,
+// strictly increasing in [0, T]) in one pass; outputs [B][K] (each nullable).  The curve form
+// of the pipelined kernel where ocx_pipe_supported(L), of the plain kernel otherwise; then
+// the streamed comparator of the pairs the closed form (onepass) did not take, from ws
+// (ocx_curve_ws_bytes(L, K) bytes of device memory).
+int64_t ocx_curve_ws_bytes(const ocx_layout* L, int64_t K);
+hipError_t ocx_launch_alg_curve(const ocx_layout* L, const double* zt, const double* yt, int ftl,
+                                double eta0, const int64_t* ck, int64_t K, double* reg,
+                                double* cum, double* comp, int* closed_out, int onepass,
+                                void* ws, hipStream_t st);
 // the lean form over wave-groups [g0, g0 + gn) (<= 128 VGPRs; FTRL, 8 x 8 and 16 x 4 layouts),
 // the FTRL side of the overlapped pipeline (ocx_pipeline.hip)
 bool ocx_pipe_lean_supported(const ocx_layout* L);

@@ -77,6 +77,51 @@ def simulate_alg_batch(z, y, alg_flag: int = 0, eta0: float = SQRT2, comparator=
     return reg
 
 
+def _checkpoints(checkpoints, T: int) -> np.ndarray:
+    """The checkpoint horizons of a regret curve as a contiguous int64 array: integers,
+    strictly increasing, inside [0, T] (0 and T allowed).  Raises ValueError otherwise."""
+    a = np.asarray(checkpoints)
+    if a.ndim != 1:
+        raise ValueError(f"checkpoints must be one-dimensional, got shape {a.shape}")
+    if a.size and not (np.issubdtype(a.dtype, np.integer) or np.all(a == np.floor(a))):
+        raise ValueError("checkpoints must be integers")
+    ck = np.ascontiguousarray(a, dtype=np.int64)
+    if ck.size and (ck.min() < 0 or ck.max() > int(T)):
+        raise ValueError(f"checkpoints must lie in [0, T = {int(T)}], got {ck.min()}..{ck.max()}")
+    if np.any(np.diff(ck) <= 0):
+        raise ValueError("checkpoints must be strictly increasing")
+    return ck
+
+
+def simulate_alg_curve_batch(z, y, checkpoints, alg_flag: int = 0, eta0: float = SQRT2, *,
+                             lanes_per_seq: int = LANES_BEST, device: int = 0,
+                             return_all: bool = False):
+    """Regret curves: fast_algorithms.py:88-115 over B sequences, observed at every horizon of
+    ``checkpoints`` (strictly increasing in [0, T]) in one pass (ocx_simulate_alg_curve_batch).
+
+    Column k is simulate_alg on (z[b, :t_k], y[b, :t_k]).  Bit-exact modes (lanes_per_seq 1 /
+    -k) stream the reference's comparator sum for every pair; the others take the closed form
+    where the kernel certifies the prefix.  Returns regret [B, K] or, with ``return_all``,
+    (regret, cum_loss, comp_loss, closed) — closed [B, K] int32, 1 where the closed form was
+    taken."""
+    z = _f64(z)
+    y = _f64(y)
+    B, T, d = _check_zy(z, y)
+    ck = _checkpoints(checkpoints, T)
+    K = int(ck.size)
+    reg = np.zeros((B, K))
+    cum = np.zeros((B, K)) if return_all else None
+    comp = np.zeros((B, K)) if return_all else None
+    closed = np.zeros((B, K), dtype=np.int32) if return_all else None
+    _lib.call("ocx_simulate_alg_curve_batch", ptr(z), ptr(y), B, T, d, int(alg_flag), float(eta0),
+              ck.ctypes.data_as(_lib.c_i64p), K, ptr(reg), ptr(cum), ptr(comp),
+              closed.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if return_all else None,
+              int(lanes_per_seq), int(device))
+    if return_all:
+        return reg, cum, comp, closed
+    return reg
+
+
 def simulate_smart_batch(z, y, thresh, eta0: float = SQRT2, *, lanes_per_seq: int = LANES_BEST,
                          device: int = 0, return_switch: bool = False):
     """fast_algorithms.py:118-164 over B sequences; thresh scalar or [B].  Bit-exact modes
@@ -547,6 +592,37 @@ class DeviceBatch:
                   closed_out.data_ptr() if closed_out is not None else None, self._sp)
         return self.regret
 
+    def simulate_alg_curve(self, checkpoints, alg_flag: int = 0, eta0: float = SQRT2,
+                           closed_comparator: Optional[bool] = None):
+        """Regret curves of the resident batch (ocx_dev_simulate_alg_curve, async): FTRL / FTL
+        observed at every horizon of ``checkpoints`` (strictly increasing in [0, T], validated
+        here) in one pass over z.  Returns device tensors ``regret``, ``cum``, ``comp``
+        (float64) and ``closed`` (int32), each [B, K]; column k is what simulate_alg gives on
+        the batch truncated at t_k, bit for bit in the same layout.  ``closed_comparator``
+        defaults as in simulate_alg; a (sequence, checkpoint) pair the kernel cannot certify
+        streams the comparator pass over its prefix."""
+        torch = self.torch
+        ck = _checkpoints(checkpoints, self.L.T)
+        K, B = int(ck.size), int(self.L.B)
+        if closed_comparator is None:
+            closed_comparator = not self.exact
+        flags = _lib.OCX_ALG_CLIPPED_ROWS if closed_comparator else 0
+        nbytes = int(_lib.load().ocx_curve_workspace_bytes(self._lp(), K))
+        if nbytes < 0:
+            _lib.check(nbytes, "ocx_curve_workspace_bytes")
+        with torch.cuda.device(self.device), self._on_stream():
+            ckd = torch.as_tensor(ck).to(self.device)
+            out = {k: torch.zeros((B, K), dtype=torch.float64, device=self.device)
+                   for k in ("regret", "cum", "comp")}
+            out["closed"] = torch.zeros((B, K), dtype=torch.int32, device=self.device)
+            ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self.device)
+        self._call("ocx_dev_simulate_alg_curve", self._lp(), self.z.data_ptr(), self.y.data_ptr(),
+                   int(alg_flag), float(eta0), ckd.data_ptr() if K else None, K,
+                   out["regret"].data_ptr(), out["cum"].data_ptr(), out["comp"].data_ptr(),
+                   out["closed"].data_ptr(), flags, ws.data_ptr(), ws.numel() * 8, self._sp)
+        self._keep_curve = self._hold(ckd, ws)
+        return out
+
     def simulate_smart(self, thresh, eta0: float = SQRT2, switch_step=None,
                        closed_prefix: Optional[bool] = None,
                        closed_comparator: Optional[bool] = None, stats=None):
@@ -745,3 +821,60 @@ class DeviceBatch:
     @property
     def y_bytes(self) -> int:
         return int(self.L.y_elems) * 8
+
+
+# HBM that gT_regret_curves' default batch keeps resident: z, y and the curve workspace
+GT_CURVE_HBM_BUDGET = 64 << 30
+
+
+def gT_regret_curves(T: int, runs: int, checkpoints, *, base_seed: int = 0, d: int = 5,
+                     eta0: float = SQRT2, run0: int = 0, lanes_per_seq: int = LANES_BEST,
+                     device: int = 0, batch: Optional[int] = None, return_closed: bool = False):
+    """Regret-against-horizon curves of FTRL on the g(T) sampler: the sequences
+    _rng(base_seed, T, run), run in [run0, run0 + runs) (fast_algorithms.py:230-241 at horizon
+    T, with a ``d`` parameter), observed at every horizon of ``checkpoints``.  Returns
+    regret [runs, K] (and closed [runs, K] int32 with ``return_closed``).
+
+    Generated on device (DeviceBatch.generate_gT) and simulated once (simulate_alg_curve) in
+    batches of ``batch`` sequences — by default as many as keep z, y and the curve workspace
+    under GT_CURVE_HBM_BUDGET bytes; a short last batch is handled.  The library's cached
+    buffers are released first.  Only the [runs, K] result crosses PCIe."""
+    import torch
+    if base_seed < 0 or base_seed >= 2 ** 64:
+        raise ValueError("base_seed must be in [0, 2**64)")
+    T, runs = int(T), int(runs)
+    if runs < 0:
+        raise ValueError("runs must be >= 0")
+    ck = _checkpoints(checkpoints, T)
+    K = int(ck.size)
+    if batch is not None and int(batch) < 1:
+        raise ValueError("batch must be >= 1")
+    if runs == 0 or K == 0:
+        empty = np.zeros((runs, K))
+        return (empty, np.zeros((runs, K), dtype=np.int32)) if return_closed else empty
+    release_buffers(device)
+    if batch is None:
+        L = _lib.layout(runs, T, d, lanes_per_seq)  # bytes per wave-group of S sequences
+        per_group = 8 * (L.z_elems + L.y_elems) // L.G + 64 * K * (8 * L.C + 12)
+        batch = max(1, GT_CURVE_HBM_BUDGET // max(per_group, 1)) * L.S
+    batch = min(int(batch), runs)
+    dev = torch.device("cuda", int(device))
+    with torch.cuda.device(dev):
+        reg = torch.empty((runs, K), dtype=torch.float64, device=dev)
+        closed = torch.empty((runs, K), dtype=torch.int32, device=dev) if return_closed else None
+        db = None
+        for r0 in range(0, runs, batch):
+            n = min(batch, runs - r0)
+            if db is None or db.L.B != n:
+                db = None  # the short last batch: free the full one first
+                db = DeviceBatch(n, T, d, lanes_per_seq=lanes_per_seq, device=int(device))
+            db.generate_gT(base_seed, int(run0) + r0)
+            res = db.simulate_alg_curve(ck, 0, eta0)
+            with db._on_stream():
+                reg[r0:r0 + n].copy_(res["regret"])
+                if closed is not None:
+                    closed[r0:r0 + n].copy_(res["closed"])
+        with db._on_stream():
+            out = reg.cpu().numpy()
+            cl = closed.cpu().numpy() if closed is not None else None
+    return (out, cl) if return_closed else out
