@@ -57,7 +57,9 @@
  * ocx_dev_gen_simulate (generation overlapped with FTRL); nothing existing changed.
  * The regret-curve symbols (ocx_curve_workspace_bytes, ocx_dev_simulate_alg_curve,
  * ocx_simulate_alg_curve_batch) were added without a version change: the number stays 400 and
- * nothing existing changed; a caller that needs them looks the symbols up.
+ * nothing existing changed; a caller that needs them looks the symbols up.  The same holds for
+ * the step-size sweep symbols (ocx_etas_group, ocx_dev_simulate_alg_etas,
+ * ocx_simulate_alg_etas_batch).
  *
  * Checking the ABI: one intermediate 0.1.x tree exported ocx_ftrl_vs_exact_batch WITH a
  * `norm` argument under the same symbol and the same version number as the release without
@@ -383,6 +385,41 @@ int ocx_simulate_alg_curve_batch(const double* z, const double* y, int64_t B, in
                                  int alg_flag, double eta0, const int64_t* checkpoints, int64_t K,
                                  double* regret, double* cum_loss, double* comp_loss,
                                  int32_t* closed_out, int lanes_per_seq, int device);
+
+/* Step-size sweeps: FTRL (fast_algorithms.py:88-115, alg_flag 0) for M values of eta0 in
+ * passes over z that each serve a group of them.  For every m,
+ *   regret[b][m], cum_loss[b][m], comp_loss[b][m], closed_out[b][m]
+ * are bit for bit what ocx_dev_simulate_alg_ex gives with alg_flag 0, eta0 = etas[m],
+ * comparator = x_last = NULL, the same layout and the same flags; they do not depend on the
+ * group size in use.  FTRL only (FTL has no step size); no caller comparator, no x_last.
+ * etas: any values, any order, duplicates allowed (equal values give equal columns).
+ *
+ * step sizes one pass over z serves in layout L (1: the single-eta form, once per step size;
+ * negative ocx_status on error).  Above 1 only where that group measured faster than M
+ * single-eta passes; never above the smallest group that holds M. */
+int ocx_etas_group(const ocx_layout* L, int64_t M);
+
+/* device: etas is a HOST array [M], read at call time (it travels in the kernel arguments);
+ * regret / cum_loss / comp_loss: device [B][M] row-major, each nullable;
+ * closed_out [B][M] int32 nullable (1 = closed form taken);
+ * flags: 0, or OCX_ALG_CLOSED_COMPARATOR / OCX_ALG_CLIPPED_ROWS (one request, as in
+ * ocx_dev_simulate_alg_ex).  The certificate is per (sequence, eta): the row check is shared,
+ * the sub-gradient check is per column; an uncertified pair gets the streamed second pass
+ * (z read once per group, not once per column), bit-identical to flags 0, and a certified
+ * pair keeps the closed form whatever shares its wave or its group;
+ * M == 0, B == 0 and T == 0 are valid (T == 0 gives zeros);
+ * asynchronous, no allocation, no sync: capture-safe like the other dev entry points. */
+int ocx_dev_simulate_alg_etas(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                              const double* etas, int64_t M, double* regret, double* cum_loss,
+                              double* comp_loss, int32_t* closed_out, int flags, void* stream);
+
+/* host: numpy buffers in, [B][M] out; M >= 0 is validated before any device is touched.
+ * Bit-exact layouts (lanes_per_seq 1 / -k): streamed comparator for every pair;
+ * other modes: closed form where certified. */
+int ocx_simulate_alg_etas_batch(const double* z, const double* y, int64_t B, int64_t T, int64_t d,
+                                const double* etas, int64_t M, double* regret, double* cum_loss,
+                                double* comp_loss, int32_t* closed_out, int lanes_per_seq,
+                                int device);
 
 /* ocx_ftl_exact_batch on device (`norm` 0 l2, 1 l1, 2 linf). */
 int ocx_dev_ftl_exact(const ocx_layout* L, const double* z_tiled, const double* y_tiled, int norm,

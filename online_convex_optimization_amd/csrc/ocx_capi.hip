@@ -426,6 +426,63 @@ int ocx_dev_simulate_alg_curve(const ocx_layout* L, const double* z_tiled, const
     return OCX_OK;
 }
 
+// the smallest instantiated group that holds M step sizes, capped at `best`
+static int etas_group_for(const ocx_layout* L, int64_t M, int best) {
+    int g = best;
+    while (g > 1 && (g / 2 >= M || !ocx_etas_instance(L, g))) g /= 2;
+    return g;
+}
+
+int ocx_etas_group(const ocx_layout* L, int64_t M) {
+    if (int rc = check_layout(L)) return rc;
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    return etas_group_for(L, M, ocx_etas_best_group(L));
+}
+
+// group 0: the dispatcher's choice
+static int dev_simulate_alg_etas(const ocx_layout* L, const double* z_tiled,
+                                 const double* y_tiled, const double* etas, int64_t M,
+                                 double* regret, double* cum_loss, double* comp_loss,
+                                 int32_t* closed_out, int flags, int group, void* stream) {
+    StreamDevice sd_(stream);
+    if (int rc = check_layout(L)) return rc;
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    if (M > 0 && !etas) return fail(OCX_E_INVALID, "NULL etas");
+    if (flags & ~(OCX_ALG_CLIPPED_ROWS | OCX_ALG_CLOSED_COMPARATOR))
+        return fail(OCX_E_INVALID, "unknown flags");
+    if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL input buffer");
+    if (group != 0 && group != 1 && group != 2 && group != 4)
+        return fail(OCX_E_INVALID, "group must be 1, 2 or 4");
+    if (group != 0 && !ocx_etas_instance(L, group))
+        return fail(OCX_E_UNSUPPORTED, "no group-" + std::to_string(group) + " form at " +
+                                           std::to_string(L->C) + " coordinates per lane");
+    if (M == 0 || L->B == 0) return OCX_OK;
+    if (group == 0) group = etas_group_for(L, M, ocx_etas_best_group(L));
+    // the two flags are one request: the kernel certifies every row and sub-gradient itself
+    OCX_HIP(ocx_launch_alg_etas(L, z_tiled, y_tiled, etas, M, regret, cum_loss, comp_loss,
+                                closed_out,
+                                (flags & (OCX_ALG_CLIPPED_ROWS | OCX_ALG_CLOSED_COMPARATOR)) ? 1 : 0,
+                                group, (hipStream_t)stream));
+    return OCX_OK;
+}
+
+int ocx_dev_simulate_alg_etas(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                              const double* etas, int64_t M, double* regret, double* cum_loss,
+                              double* comp_loss, int32_t* closed_out, int flags, void* stream) {
+    return dev_simulate_alg_etas(L, z_tiled, y_tiled, etas, M, regret, cum_loss, comp_loss,
+                                 closed_out, flags, 0, stream);
+}
+
+int ocx_test_simulate_alg_etas(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                               const double* etas, int64_t M, double* regret, double* cum_loss,
+                               double* comp_loss, int32_t* closed_out, int flags, int group,
+                               void* stream) {
+    if (group != 1 && group != 2 && group != 4)
+        return fail(OCX_E_INVALID, "group must be 1, 2 or 4");
+    return dev_simulate_alg_etas(L, z_tiled, y_tiled, etas, M, regret, cum_loss, comp_loss,
+                                 closed_out, flags, group, stream);
+}
+
 int ocx_dev_ftl_exact(const ocx_layout* L, const double* z_tiled, const double* y_tiled, int norm,
                       double* cum_loss, double* comp_loss, double* cmp_action, int32_t* regime,
                       void* stream) {
@@ -694,6 +751,48 @@ int ocx_simulate_alg_curve_batch(const double* z, const double* y, int64_t B, in
     if (cum_loss) std::memcpy(cum_loss, h.data() + nk, nk * 8);
     if (comp_loss) std::memcpy(comp_loss, h.data() + 2 * nk, nk * 8);
     if (closed_out) std::memcpy(closed_out, h.data() + 3 * nk, nk * 4);
+    return OCX_OK;
+}
+
+int ocx_simulate_alg_etas_batch(const double* z, const double* y, int64_t B, int64_t T, int64_t d,
+                                const double* etas, int64_t M, double* regret, double* cum_loss,
+                                double* comp_loss, int32_t* closed_out, int lanes_per_seq,
+                                int device) {
+    ocx_layout L;
+    if (int rc = ocx_layout_init(B, T, d, lanes_per_seq, &L)) return rc;
+    // everything about the step sizes before any device or data pointer is touched
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    if (M > 0 && !etas) return fail(OCX_E_INVALID, "NULL etas");
+    if (B == 0 || M == 0) return OCX_OK;
+    if ((T * d > 0 && !z) || (T > 0 && !y)) return fail(OCX_E_INVALID, "NULL z/y");
+    DevCtx* cx;
+    if (int rc = ctx_enter(device, &cx)) return rc;
+    std::lock_guard<std::mutex> lk(cx->mu);
+    hipStream_t st = cx->stream;
+    const size_t nz = (size_t)(B * T * d), ny = (size_t)(B * T), nm = (size_t)(B * M);
+    OCX_HIP(cx->zraw.ensure(nz * 8));
+    OCX_HIP(cx->yraw.ensure(ny * 8));
+    OCX_HIP(cx->zt.ensure((size_t)L.z_elems * 8));
+    OCX_HIP(cx->yt.ensure((size_t)L.y_elems * 8));
+    OCX_HIP(cx->out.ensure(nm * (3 * 8 + 4)));
+    if (nz) OCX_HIP(hipMemcpyAsync(cx->zraw.p, z, nz * 8, hipMemcpyHostToDevice, st));
+    if (ny) OCX_HIP(hipMemcpyAsync(cx->yraw.p, y, ny * 8, hipMemcpyHostToDevice, st));
+    OCX_HIP(ocx_launch_pack(&L, cx->zraw.as<double>(), cx->yraw.as<double>(), cx->zt.as<double>(),
+                            cx->yt.as<double>(), st));
+    double* o = cx->out.as<double>();
+    int32_t* oc = reinterpret_cast<int32_t*>(o + 3 * nm);
+    // bit-exact modes keep the reference's streamed comparator sum for every pair
+    const int flags = (lanes_per_seq == 1 || lanes_per_seq < 0) ? 0 : OCX_ALG_CLOSED_COMPARATOR;
+    if (int rc = ocx_dev_simulate_alg_etas(&L, cx->zt.as<double>(), cx->yt.as<double>(), etas, M,
+                                           o, o + nm, o + 2 * nm, oc, flags, st))
+        return rc;
+    std::vector<double> h(3 * nm + (nm + 1) / 2);
+    OCX_HIP(hipMemcpyAsync(h.data(), o, nm * (3 * 8 + 4), hipMemcpyDeviceToHost, st));
+    OCX_HIP(hipStreamSynchronize(st));
+    if (regret) std::memcpy(regret, h.data(), nm * 8);
+    if (cum_loss) std::memcpy(cum_loss, h.data() + nm, nm * 8);
+    if (comp_loss) std::memcpy(comp_loss, h.data() + 2 * nm, nm * 8);
+    if (closed_out) std::memcpy(closed_out, h.data() + 3 * nm, nm * 4);
     return OCX_OK;
 }
 

@@ -29,6 +29,16 @@ hipError_t ocx_launch_alg_curve(const ocx_layout* L, const double* zt, const dou
                                 double eta0, const int64_t* ck, int64_t K, double* reg,
                                 double* cum, double* comp, int* closed_out, int onepass,
                                 void* ws, hipStream_t st);
+// Step-size sweeps (ocx_alg_etas.hip): FTRL for the M step sizes etas (HOST, read at call
+// time) in passes of at most `group` (1, 2 or 4; ocx_etas_instance) columns; outputs [B][M]
+// (each nullable).  The multi-η form of the pipelined kernel where ocx_pipe_supported(L), of
+// the plain kernel otherwise.  ocx_etas_best_group: the group the measurements chose.
+bool ocx_etas_instance(const ocx_layout* L, int group);
+int ocx_etas_best_group(const ocx_layout* L);
+hipError_t ocx_launch_alg_etas(const ocx_layout* L, const double* zt, const double* yt,
+                               const double* etas, int64_t M, double* reg, double* cum,
+                               double* comp, int* closed_out, int onepass, int group,
+                               hipStream_t st);
 // the lean form over wave-groups [g0, g0 + gn) (<= 128 VGPRs; FTRL, 8 x 8 and 16 x 4 layouts),
 // the FTRL side of the overlapped pipeline (ocx_pipeline.hip)
 bool ocx_pipe_lean_supported(const ocx_layout* L);

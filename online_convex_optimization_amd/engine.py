@@ -122,6 +122,48 @@ def simulate_alg_curve_batch(z, y, checkpoints, alg_flag: int = 0, eta0: float =
     return reg
 
 
+def _etas(etas) -> np.ndarray:
+    """The step sizes of a sweep as a contiguous float64 array: a one-dimensional list of real
+    numbers (any values, any order, duplicates allowed).  Raises ValueError otherwise."""
+    try:
+        a = np.asarray(etas)
+    except Exception as e:  # ragged lists
+        raise ValueError(f"etas must be a one-dimensional list of real numbers: {e}") from None
+    if a.ndim != 1:
+        raise ValueError(f"etas must be one-dimensional, got shape {a.shape}")
+    if a.size and not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise ValueError(f"etas must be real numbers, got dtype {a.dtype}")
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def simulate_alg_etas_batch(z, y, etas, *, lanes_per_seq: int = LANES_BEST, device: int = 0,
+                            return_all: bool = False):
+    """Step-size sweep: FTRL (fast_algorithms.py:88-115) over B sequences for every eta0 of
+    ``etas``, each pass over z serving a group of them (ocx_simulate_alg_etas_batch).
+
+    Column m is simulate_alg with eta0 = etas[m], bit for bit in the same layout.  Bit-exact
+    modes (lanes_per_seq 1 / -k) stream the reference's comparator sum for every pair; the
+    others take the closed form where the kernel certifies the (sequence, eta) pair.  Returns
+    regret [B, M] or, with ``return_all``, (regret, cum_loss, comp_loss, closed) — closed
+    [B, M] int32, 1 where the closed form was taken."""
+    z = _f64(z)
+    y = _f64(y)
+    B, T, d = _check_zy(z, y)
+    et = _etas(etas)
+    M = int(et.size)
+    reg = np.zeros((B, M))
+    cum = np.zeros((B, M)) if return_all else None
+    comp = np.zeros((B, M)) if return_all else None
+    closed = np.zeros((B, M), dtype=np.int32) if return_all else None
+    _lib.call("ocx_simulate_alg_etas_batch", ptr(z), ptr(y), B, T, d, ptr(et), M, ptr(reg),
+              ptr(cum), ptr(comp),
+              closed.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if return_all else None,
+              int(lanes_per_seq), int(device))
+    if return_all:
+        return reg, cum, comp, closed
+    return reg
+
+
 def simulate_smart_batch(z, y, thresh, eta0: float = SQRT2, *, lanes_per_seq: int = LANES_BEST,
                          device: int = 0, return_switch: bool = False):
     """fast_algorithms.py:118-164 over B sequences; thresh scalar or [B].  Bit-exact modes
@@ -623,6 +665,34 @@ class DeviceBatch:
         self._keep_curve = self._hold(ckd, ws)
         return out
 
+    def simulate_alg_etas(self, etas, closed_comparator: Optional[bool] = None, *, _group=None):
+        """Step-size sweep of the resident batch (ocx_dev_simulate_alg_etas, async): FTRL for
+        every eta0 of ``etas`` (a one-dimensional list of real numbers, validated here), each
+        pass over z serving ocx_etas_group(L, M) of them.  Returns device tensors ``regret``,
+        ``cum``, ``comp`` (float64) and ``closed`` (int32), each [B, M]; column m is what
+        simulate_alg(0, etas[m]) gives, bit for bit in the same layout.  ``closed_comparator``
+        defaults as in simulate_alg; a (sequence, eta) pair the kernel cannot certify streams
+        the comparator pass.  (``_group``: tests and tools/etas_probe.py force the group size
+        through include/ocx_testing.h.)"""
+        torch = self.torch
+        et = _etas(etas)
+        M, B = int(et.size), int(self.L.B)
+        if closed_comparator is None:
+            closed_comparator = not self.exact
+        flags = _lib.OCX_ALG_CLIPPED_ROWS if closed_comparator else 0
+        with torch.cuda.device(self.device), self._on_stream():
+            out = {k: torch.zeros((B, M), dtype=torch.float64, device=self.device)
+                   for k in ("regret", "cum", "comp")}
+            out["closed"] = torch.zeros((B, M), dtype=torch.int32, device=self.device)
+        args = (self._lp(), self.z.data_ptr(), self.y.data_ptr(), ptr(et), M,
+                out["regret"].data_ptr(), out["cum"].data_ptr(), out["comp"].data_ptr(),
+                out["closed"].data_ptr(), flags)
+        if _group is None:
+            self._call("ocx_dev_simulate_alg_etas", *args, self._sp)
+        else:
+            self._call("ocx_test_simulate_alg_etas", *args, int(_group), self._sp)
+        return out
+
     def simulate_smart(self, thresh, eta0: float = SQRT2, switch_step=None,
                        closed_prefix: Optional[bool] = None,
                        closed_comparator: Optional[bool] = None, stats=None):
@@ -870,6 +940,59 @@ def gT_regret_curves(T: int, runs: int, checkpoints, *, base_seed: int = 0, d: i
                 db = DeviceBatch(n, T, d, lanes_per_seq=lanes_per_seq, device=int(device))
             db.generate_gT(base_seed, int(run0) + r0)
             res = db.simulate_alg_curve(ck, 0, eta0)
+            with db._on_stream():
+                reg[r0:r0 + n].copy_(res["regret"])
+                if closed is not None:
+                    closed[r0:r0 + n].copy_(res["closed"])
+        with db._on_stream():
+            out = reg.cpu().numpy()
+            cl = closed.cpu().numpy() if closed is not None else None
+    return (out, cl) if return_closed else out
+
+
+def gT_regrets_etas(T: int, runs: int, etas, *, base_seed: int = 0, d: int = 5, run0: int = 0,
+                    lanes_per_seq: int = LANES_BEST, device: int = 0,
+                    batch: Optional[int] = None, return_closed: bool = False):
+    """FTRL's regrets on the g(T) sampler for every eta0 of ``etas``: the sequences
+    _rng(base_seed, T, run), run in [run0, run0 + runs) (fast_algorithms.py:230-241 with a
+    ``d`` parameter).  Returns regret [runs, M] (and closed [runs, M] int32 with
+    ``return_closed``); column m is gT_regrets(..., eta0=etas[m]).
+
+    Each batch is generated once on device (DeviceBatch.generate_gT) and simulated for all M
+    step sizes (simulate_alg_etas), in batches of ``batch`` sequences — by default as many as
+    keep z and y under GT_CURVE_HBM_BUDGET bytes; a short last batch is handled.  The
+    library's cached buffers are released first.  Only the [runs, M] result crosses PCIe."""
+    import torch
+    if base_seed < 0 or base_seed >= 2 ** 64:
+        raise ValueError("base_seed must be in [0, 2**64)")
+    T, runs = int(T), int(runs)
+    if runs < 0:
+        raise ValueError("runs must be >= 0")
+    et = _etas(etas)
+    M = int(et.size)
+    if batch is not None and int(batch) < 1:
+        raise ValueError("batch must be >= 1")
+    if runs == 0 or M == 0:
+        empty = np.zeros((runs, M))
+        return (empty, np.zeros((runs, M), dtype=np.int32)) if return_closed else empty
+    release_buffers(device)
+    if batch is None:
+        L = _lib.layout(runs, T, d, lanes_per_seq)  # bytes per wave-group of S sequences
+        per_group = 8 * (L.z_elems + L.y_elems) // L.G
+        batch = max(1, GT_CURVE_HBM_BUDGET // max(per_group, 1)) * L.S
+    batch = min(int(batch), runs)
+    dev = torch.device("cuda", int(device))
+    with torch.cuda.device(dev):
+        reg = torch.empty((runs, M), dtype=torch.float64, device=dev)
+        closed = torch.empty((runs, M), dtype=torch.int32, device=dev) if return_closed else None
+        db = None
+        for r0 in range(0, runs, batch):
+            n = min(batch, runs - r0)
+            if db is None or db.L.B != n:
+                db = None  # the short last batch: free the full one first
+                db = DeviceBatch(n, T, d, lanes_per_seq=lanes_per_seq, device=int(device))
+            db.generate_gT(base_seed, int(run0) + r0)
+            res = db.simulate_alg_etas(et)
             with db._on_stream():
                 reg[r0:r0 + n].copy_(res["regret"])
                 if closed is not None:
