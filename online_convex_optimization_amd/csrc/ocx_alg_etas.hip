@@ -15,8 +15,10 @@
 // arithmetic is that of the kernel it is derived from, operation for operation (the same
 // device functions in the plain form; the same fma placement, 64-step U refresh and rescale
 // test in the pipelined form), so column m carries the bits of a run of those kernels with
-// eta0 = etas[m].  The pipelined form's rescale-test shortcut is decided per column (a ballot
-// of that column's test): both of its branches give the same bits, see ocx_alg_pipe.hip.
+// eta0 = etas[m].  (Their loops stay written out: as calls to the pieces of ocx_alg_step.h two
+// measured cases ran 0.5-1.1 % slower)  The pipelined form's rescale-test
+// shortcut is decided per column (a ballot of that column's test): both of its branches give
+// the same bits, see ocx_alg_pipe.hip.
 //
 // Comparator: the loss of FTL(θ_T^m), per column.  With the closed form requested it is
 // T/2 − ||θ_T^m|| where column m's certificate holds — the row check is shared, the
@@ -33,17 +35,11 @@
 // single-η form with strided outputs: the group-1 path of every layout.
 //
 // Instances: NE = 1 for every layout; NE = 2 up to 16 coordinates per lane; NE = 4 up to 8.
-#include <cstdlib>
-#include <type_traits>
-
+#include "ocx_alg_pipe.h"
 #include "ocx_device_math.h"
 #include "ocx_dispatch.h"
 #include "ocx_internal.h"
 #include "ocx_sim_kernels.h"
-
-#ifndef OCX_PIPE_IT32_MAXC  // ocx_alg_pipe.hip's step-counter rule
-#define OCX_PIPE_IT32_MAXC 4
-#endif
 
 namespace {
 
@@ -62,16 +58,6 @@ struct EtasArgs {
     int* closed_out;
     int onepass;
 };
-
-// ocx_alg_pipe.hip's wave-group mapping (ocx_pipe_wave_id): the last blocks hold W − 1 groups
-// each instead of one short block; a spare slot gets gn and exits
-__device__ __forceinline__ int64_t etas_pipe_wave_id(int64_t gn) {
-    const int64_t W = blockDim.x >> 6, blk = blockIdx.x, w = threadIdx.x >> 6;
-    const int64_t idle = (int64_t)gridDim.x * W - gn;
-    const int64_t full = (int64_t)gridDim.x - idle;
-    if (idle <= 0 || full < 0 || blk < full) return blk * W + w;
-    return w < W - 1 ? full * W + (blk - full) * (W - 1) + w : gn;
-}
 
 // Comparator and outputs of both loop forms, th = θ_T per column.  Whole wave active.  `load`
 // and the ring (zb, yb) are the loop's own, for the streamed pass.
@@ -238,11 +224,11 @@ __global__ __launch_bounds__(OCX_BLOCK, 1) void ocx_alg_etas_kernel(EtasArgs a) 
 template <int C, int P, int NB, bool RT, int NE>
 __global__ __launch_bounds__(OCX_BLOCK, 1) void ocx_alg_pipe_etas_kernel(EtasArgs a) {
     static_assert(P >= 2 && NB >= 4, "butterfly layouts, a ring holding z_{t-1} .. z_{t+1}");
-    using IT = typename std::conditional<(C <= OCX_PIPE_IT32_MAXC), int, int64_t>::type;
+    using IT = pipe_step_t<C>;
     constexpr int S = 64 / P;
     constexpr int K2 = C / 2;
     const int lane = threadIdx.x & 63;
-    const int64_t g = (int64_t)__builtin_amdgcn_readfirstlane((int)etas_pipe_wave_id(a.G));
+    const int64_t g = (int64_t)__builtin_amdgcn_readfirstlane((int)ocx_pipe_wave_id(a.G));
     if (g >= a.G) return;
     const int64_t T = a.T;
     const int s = lane / P;
@@ -428,54 +414,28 @@ hipError_t launch_plain_etas(const ocx_layout* L, const EtasArgs& a, int NE, hip
     OCX_DISPATCH(launch_etas4_cp, L, a, st)
 }
 
-// ocx_alg_pipe.hip's choices: four-wave blocks from four groups on, a ring one slot deeper
-// than the plain kernel's, the rescale test everywhere but the 8 x 8 full form
 template <int C, int P, int NE>
 hipError_t launch_pipe_etas_cpn(const ocx_layout* L, const EtasArgs& a, hipStream_t st) {
     if constexpr (etas_instance(C, NE)) {
-        constexpr int NB = nb_for(C, P) + 1 < 4 ? 4 : nb_for(C, P) + 1;
-        constexpr bool RT = !(C == 8 && P == 8);
-        const int bw =
-            std::getenv("OCX_BLOCK_WAVES") ? ocx_block_waves(L->G) : (L->G >= 4 ? 4 : 1);
-        hipLaunchKernelGGL((ocx_alg_pipe_etas_kernel<C, P, NB, RT, NE>), ocx_grid(L->G, bw),
-                           dim3(64 * bw), 0, st, a);
+        const int bw = pipe_block_waves(L->G);
+        hipLaunchKernelGGL((ocx_alg_pipe_etas_kernel<C, P, pipe_nb<C>(P), pipe_rt<C, P, 1>(), NE>),
+                           ocx_grid(L->G, bw), dim3(64 * bw), 0, st, a);
         return hipGetLastError();
     } else {
         return hipErrorInvalidValue;
     }
 }
 
-template <int C, int P>
-hipError_t launch_pipe_etas_cp(const ocx_layout* L, const EtasArgs& a, int NE, hipStream_t st) {
-    switch (NE) {
-        case 1: return launch_pipe_etas_cpn<C, P, 1>(L, a, st);
-        case 2: return launch_pipe_etas_cpn<C, P, 2>(L, a, st);
-        case 4: return launch_pipe_etas_cpn<C, P, 4>(L, a, st);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-template <int C>
-hipError_t launch_pipe_etas_c(const ocx_layout* L, const EtasArgs& a, int NE, hipStream_t st) {
-    switch (L->P) {
-        case 8: return launch_pipe_etas_cp<C, 8>(L, a, NE, st);
-        case 16: return launch_pipe_etas_cp<C, 16>(L, a, NE, st);
-        case 32: return launch_pipe_etas_cp<C, 32>(L, a, NE, st);
-        case 64:
-            if constexpr (C == 16) return launch_pipe_etas_cp<16, 64>(L, a, NE, st);
-            return hipErrorInvalidValue;
-        default: return hipErrorInvalidValue;
-    }
-}
-
 hipError_t launch_pipe_etas(const ocx_layout* L, const EtasArgs& a, int NE, hipStream_t st) {
-    switch (L->C) {
-        case 4: return launch_pipe_etas_c<4>(L, a, NE, st);
-        case 8: return launch_pipe_etas_c<8>(L, a, NE, st);
-        case 16: return launch_pipe_etas_c<16>(L, a, NE, st);
-        case 32: return launch_pipe_etas_c<32>(L, a, NE, st);
-        default: return hipErrorInvalidValue;
-    }
+    return ocx_pipe_dispatch(L, [&](auto c, auto p) {
+        constexpr int C = decltype(c)::value, P = decltype(p)::value;
+        switch (NE) {
+            case 1: return launch_pipe_etas_cpn<C, P, 1>(L, a, st);
+            case 2: return launch_pipe_etas_cpn<C, P, 2>(L, a, st);
+            case 4: return launch_pipe_etas_cpn<C, P, 4>(L, a, st);
+            default: return hipErrorInvalidValue;
+        }
+    });
 }
 
 }  // namespace
@@ -512,12 +472,7 @@ hipError_t ocx_launch_alg_etas(const ocx_layout* L, const double* zt, const doub
     a.comp_out = comp;
     a.closed_out = closed_out;
     a.onepass = onepass;
-    // ocx_launch_alg's rule (OCX_ALG_NO_PIPE=1: the plain form, for A/B measurements)
-    static const bool no_pipe = [] {
-        const char* e = std::getenv("OCX_ALG_NO_PIPE");
-        return e && std::atoi(e) != 0;
-    }();
-    const bool pipe = !no_pipe && ocx_pipe_supported(L);
+    const bool pipe = ocx_alg_use_pipe(L);
     for (int64_t m0 = 0; m0 < M; m0 += group) {
         const int ne = (int)(M - m0 < group ? M - m0 : group);
         const int NE = ne <= 1 ? 1 : (ne <= 2 ? 2 : 4);  // the smallest instance that holds them
