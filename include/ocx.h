@@ -59,7 +59,8 @@
  * ocx_simulate_alg_curve_batch) were added without a version change: the number stays 400 and
  * nothing existing changed; a caller that needs them looks the symbols up.  The same holds for
  * the step-size sweep symbols (ocx_etas_group, ocx_dev_simulate_alg_etas,
- * ocx_simulate_alg_etas_batch).
+ * ocx_simulate_alg_etas_batch) and the threshold sweep symbols (ocx_smart_thresholds_group,
+ * ocx_dev_simulate_smart_thresholds, ocx_simulate_smart_thresholds_batch).
  *
  * Checking the ABI: one intermediate 0.1.x tree exported ocx_ftrl_vs_exact_batch WITH a
  * `norm` argument under the same symbol and the same version number as the release without
@@ -479,6 +480,45 @@ int ocx_dev_simulate_smart_ex(const ocx_layout* L, const double* z_tiled, const 
                               const double* thresh, double eta0, double* regret,
                               int64_t* switch_step, int flags, unsigned long long* stats,
                               void* stream);
+
+/* Threshold sweeps: SMART (fast_algorithms.py:118-164) for M switch thresholds in passes over
+ * z that each serve a group of them.  The FTL leg, the prefix loss of the switch test and the
+ * final comparator do not depend on the threshold and are formed once per pass; the switch
+ * step, the FTRL state after it and total_loss are per column.  For every m,
+ *   regret[b][m], switch_step[b][m]
+ * are bit for bit what ocx_dev_simulate_smart_ex's lane-group kernel gives with
+ * thresh[b] = thresh[b][m], the same layout and the same flags; they do not depend on the
+ * group size in use.  thresh = +inf makes a column FTL's regret (the column never switches:
+ * the same adds, the same comparator); sqrt(2T) and the empirical g(T) are the drivers' SMART
+ * and EMP columns.  NaN and ±inf are legal thresholds (NaN and +inf never switch, -inf
+ * switches at step 0), any order, duplicates allowed.
+ *
+ * thresholds one pass over z serves in layout L (1: once per threshold; negative ocx_status
+ * on error).  Above 1 only where that group measured faster than M single-threshold passes
+ * (DESIGN.md 3.11); never above the smallest group that holds M. */
+int ocx_smart_thresholds_group(const ocx_layout* L, int64_t M);
+
+/* device: thresh is a DEVICE array [B][M] row-major (per-sequence thresholds); regret [B][M]
+ * device, switch_step [B][M] int64 device, nullable (-1 = never switched);
+ * flags: those of ocx_dev_simulate_smart_ex (OCX_SMART_CLOSED_PREFIX,
+ * OCX_ALG_CLOSED_COMPARATOR / OCX_ALG_CLIPPED_ROWS); unknown flags are rejected.  A step
+ * whose closed-form prefix leaves some column undecided re-scans the prefix once for all of
+ * them.  stats (nullable, device uint64 [2]), per launch (ceil(M / group) launches):
+ * += (sequence, step) pairs that re-scanned, += sequences that took the closed comparator.
+ * M == 0, B == 0 and T == 0 are valid (T == 0 gives zeros and -1);
+ * asynchronous, no allocation, no sync: capture-safe like the other dev entry points. */
+int ocx_dev_simulate_smart_thresholds(const ocx_layout* L, const double* z_tiled,
+                                      const double* y_tiled, const double* thresh, int64_t M,
+                                      double eta0, double* regret, int64_t* switch_step,
+                                      int flags, unsigned long long* stats, void* stream);
+
+/* host: numpy buffers in, [B][M] out; thresh is a HOST array [B][M]; switch_step nullable.
+ * Bit-exact layouts (lanes_per_seq 1 / -k): flags 0, the reference's prefix re-scan (once per
+ * step for the group's columns) and streamed comparator; other modes: both closed forms. */
+int ocx_simulate_smart_thresholds_batch(const double* z, const double* y, int64_t B, int64_t T,
+                                        int64_t d, const double* thresh, int64_t M, double eta0,
+                                        double* regret, int64_t* switch_step, int lanes_per_seq,
+                                        int device);
 
 /* exact_ftl.py:306-333 on device; a_tiled is the actions [B][T+1][d] tiled with a
  * layout of T+1 steps (z/y use L, actions use La with La->T == L->T + 1). */

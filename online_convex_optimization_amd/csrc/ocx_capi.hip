@@ -579,6 +579,66 @@ int ocx_dev_simulate_smart_ex(const ocx_layout* L, const double* z_tiled, const 
     return OCX_OK;
 }
 
+// the smallest instantiated group that holds M thresholds, capped at `best`
+static int thresholds_group_for(const ocx_layout* L, int64_t M, int best) {
+    int g = best;
+    while (g > 1 && (g / 2 >= M || !ocx_thresholds_instance(L, g))) g /= 2;
+    return g;
+}
+
+int ocx_smart_thresholds_group(const ocx_layout* L, int64_t M) {
+    if (int rc = check_layout(L)) return rc;
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    return thresholds_group_for(L, M, ocx_thresholds_best_group(L));
+}
+
+// group 0: the dispatcher's choice
+static int dev_simulate_smart_thresholds(const ocx_layout* L, const double* z_tiled,
+                                         const double* y_tiled, const double* thresh, int64_t M,
+                                         double eta0, double* regret, int64_t* switch_step,
+                                         int flags, unsigned long long* stats, int group,
+                                         void* stream) {
+    StreamDevice sd_(stream);
+    if (int rc = check_layout(L)) return rc;
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    if (flags & ~(OCX_SMART_CLOSED_PREFIX | OCX_ALG_CLOSED_COMPARATOR | OCX_ALG_CLIPPED_ROWS))
+        return fail(OCX_E_INVALID, "unknown flags");
+    if (group != 0 && group != 1 && group != 2 && group != 4)
+        return fail(OCX_E_INVALID, "group must be 1, 2 or 4");
+    if (group != 0 && !ocx_thresholds_instance(L, group))
+        return fail(OCX_E_UNSUPPORTED, "no group-" + std::to_string(group) + " form at " +
+                                           std::to_string(L->C) + " coordinates per lane");
+    if (M == 0 || L->G == 0) return OCX_OK;
+    if (!thresh || !regret) return fail(OCX_E_INVALID, "NULL thresh/regret");
+    if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL input buffer");
+    if (group == 0) group = thresholds_group_for(L, M, ocx_thresholds_best_group(L));
+    OCX_HIP(ocx_launch_smart_thresholds(
+        L, z_tiled, y_tiled, thresh, M, eta0, regret, switch_step,
+        (flags & OCX_SMART_CLOSED_PREFIX) ? 1 : 0,
+        (flags & (OCX_ALG_CLOSED_COMPARATOR | OCX_ALG_CLIPPED_ROWS)) ? 1 : 0, stats, group,
+        (hipStream_t)stream));
+    return OCX_OK;
+}
+
+int ocx_dev_simulate_smart_thresholds(const ocx_layout* L, const double* z_tiled,
+                                      const double* y_tiled, const double* thresh, int64_t M,
+                                      double eta0, double* regret, int64_t* switch_step,
+                                      int flags, unsigned long long* stats, void* stream) {
+    return dev_simulate_smart_thresholds(L, z_tiled, y_tiled, thresh, M, eta0, regret,
+                                         switch_step, flags, stats, 0, stream);
+}
+
+int ocx_test_simulate_smart_thresholds(const ocx_layout* L, const double* z_tiled,
+                                       const double* y_tiled, const double* thresh, int64_t M,
+                                       double eta0, double* regret, int64_t* switch_step,
+                                       int flags, unsigned long long* stats, int group,
+                                       void* stream) {
+    if (group != 1 && group != 2 && group != 4)
+        return fail(OCX_E_INVALID, "group must be 1, 2 or 4");
+    return dev_simulate_smart_thresholds(L, z_tiled, y_tiled, thresh, M, eta0, regret,
+                                         switch_step, flags, stats, group, stream);
+}
+
 int ocx_dev_replay(const ocx_layout* L, const ocx_layout* La, const double* z_tiled,
                    const double* y_tiled, const double* a_tiled, double* cum_loss,
                    double* comp_loss, void* stream) {
@@ -835,6 +895,50 @@ int ocx_simulate_smart_batch(const double* z, const double* y, int64_t B, int64_
     OCX_HIP(hipMemcpyAsync(regret, cx->out.p, (size_t)B * 8, hipMemcpyDeviceToHost, st));
     if (switch_step)
         OCX_HIP(hipMemcpyAsync(switch_step, cx->sw.p, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    OCX_HIP(hipStreamSynchronize(st));
+    return OCX_OK;
+}
+
+int ocx_simulate_smart_thresholds_batch(const double* z, const double* y, int64_t B, int64_t T,
+                                        int64_t d, const double* thresh, int64_t M, double eta0,
+                                        double* regret, int64_t* switch_step, int lanes_per_seq,
+                                        int device) {
+    ocx_layout L;
+    if (int rc = ocx_layout_init(B, T, d, lanes_per_seq, &L)) return rc;
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    if (B == 0 || M == 0) return OCX_OK;
+    if ((T * d > 0 && !z) || (T > 0 && !y) || !thresh || !regret)
+        return fail(OCX_E_INVALID, "NULL argument");
+    DevCtx* cx;
+    if (int rc = ctx_enter(device, &cx)) return rc;
+    std::lock_guard<std::mutex> lk(cx->mu);
+    hipStream_t st = cx->stream;
+    const size_t nz = (size_t)(B * T * d), ny = (size_t)(B * T), nm = (size_t)(B * M);
+    OCX_HIP(cx->zraw.ensure(nz * 8));
+    OCX_HIP(cx->yraw.ensure(ny * 8));
+    OCX_HIP(cx->zt.ensure((size_t)L.z_elems * 8));
+    OCX_HIP(cx->yt.ensure((size_t)L.y_elems * 8));
+    OCX_HIP(cx->thr.ensure(nm * 8));
+    OCX_HIP(cx->out.ensure(nm * 8));
+    OCX_HIP(cx->sw.ensure(nm * 8));
+    if (nz) OCX_HIP(hipMemcpyAsync(cx->zraw.p, z, nz * 8, hipMemcpyHostToDevice, st));
+    if (ny) OCX_HIP(hipMemcpyAsync(cx->yraw.p, y, ny * 8, hipMemcpyHostToDevice, st));
+    OCX_HIP(hipMemcpyAsync(cx->thr.p, thresh, nm * 8, hipMemcpyHostToDevice, st));
+    OCX_HIP(ocx_launch_pack(&L, cx->zraw.as<double>(), cx->yraw.as<double>(), cx->zt.as<double>(),
+                            cx->yt.as<double>(), st));
+    // bit-exact modes: the reference's prefix re-scan and streamed comparator; the others:
+    // guarded closed-form prefix, certified closed-form comparator
+    const int flags = (lanes_per_seq == 1 || lanes_per_seq < 0)
+                          ? 0
+                          : (OCX_SMART_CLOSED_PREFIX | OCX_ALG_CLOSED_COMPARATOR);
+    if (int rc = ocx_dev_simulate_smart_thresholds(&L, cx->zt.as<double>(), cx->yt.as<double>(),
+                                                   cx->thr.as<double>(), M, eta0,
+                                                   cx->out.as<double>(), cx->sw.as<int64_t>(),
+                                                   flags, nullptr, st))
+        return rc;
+    OCX_HIP(hipMemcpyAsync(regret, cx->out.p, nm * 8, hipMemcpyDeviceToHost, st));
+    if (switch_step)
+        OCX_HIP(hipMemcpyAsync(switch_step, cx->sw.p, nm * 8, hipMemcpyDeviceToHost, st));
     OCX_HIP(hipStreamSynchronize(st));
     return OCX_OK;
 }

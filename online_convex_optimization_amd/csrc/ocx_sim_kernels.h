@@ -125,6 +125,16 @@ hipError_t ocx_launch_smart_closed(const ocx_layout* L, const double* zt, const 
                                    const double* th, double eta0, double* reg, int64_t* sw,
                                    int closed_prefix, int closed_comp, unsigned long long* stats,
                                    hipStream_t st);
+// Threshold sweeps (ocx_smart_thresholds.hip): ocx_launch_smart_closed for the M thresholds
+// th [B][M] (device) in passes of at most `group` (1, 2 or 4; ocx_thresholds_instance)
+// columns; reg / sw [B][M] (sw nullable); stats per launch.  ocx_thresholds_best_group: the
+// group the measurements chose.
+bool ocx_thresholds_instance(const ocx_layout* L, int group);
+int ocx_thresholds_best_group(const ocx_layout* L);
+hipError_t ocx_launch_smart_thresholds(const ocx_layout* L, const double* zt, const double* yt,
+                                       const double* th, int64_t M, double eta0, double* reg,
+                                       int64_t* sw, int closed_prefix, int closed_comp,
+                                       unsigned long long* stats, int group, hipStream_t st);
 // SMART with one wavefront per sequence (ocx_smart_wave.hip), d <= 64
 hipError_t ocx_launch_smart_wave(const ocx_layout* L, const double* zt, const double* yt,
                                  const double* th, double eta0, double* reg, int64_t* sw,

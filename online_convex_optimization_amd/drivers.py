@@ -67,6 +67,30 @@ def case_regrets(title: str, T: int, g_emp_T: float, *, runs: int, replicates: i
     return {k: v[:B].cpu().numpy().reshape(runs, replicates) for k, v in out.items()}
 
 
+def case_threshold_regrets(title: str, T: int, thresholds, *, runs: int, replicates: int,
+                           base_seed: int = 0, d: int = 5, p: float = 0.10, block_len: int = 20,
+                           lanes_per_seq: int = 1, device: int = 0
+                           ) -> Tuple[np.ndarray, np.ndarray]:
+    """SMART's regret against its switch threshold for one case and one T: (regrets
+    [runs, replicates, M], switch_steps [runs, replicates, M], -1 = never switched) for the
+    M values of ``thresholds``, on the batch case_regrets generates (the same sequences),
+    through one threshold sweep (DeviceBatch.simulate_smart_thresholds) instead of one SMART
+    run per threshold.  ``sqrt(2T)`` and the empirical g(T) are case_regrets' SMART and EMP;
+    ``thresh = +inf`` never switches and is its FTL, with the same adds and the same
+    comparator."""
+    family, stream0 = CASE_FAMILIES[title]
+    B = runs * replicates
+    db = engine.DeviceBatch(B, T, d, lanes_per_seq=lanes_per_seq, device=device)
+    run_idx = np.repeat(np.arange(runs), replicates)
+    rep_idx = np.tile(np.arange(replicates), runs)
+    run_seeds = base_seed + 2025 * (run_idx + 1)  # fast_driver.py:88
+    db.generate_family(family, run_seeds, stream0 + rep_idx, p=p, block_len=block_len)
+    out = db.simulate_smart_thresholds(thresholds, SQRT2)
+    M = int(out["regret"].shape[1])
+    return (out["regret"].cpu().numpy().reshape(runs, replicates, M),
+            out["switch_step"].cpu().numpy().reshape(runs, replicates, M))
+
+
 def evaluate_stream_with_stats(title: str, T_grid: Sequence[int], g_emp: Mapping[int, float], *,
                                runs: int = 1, replicates: int = 1, base_seed: int = 0,
                                lanes_per_seq: int = 1, device: int = 0) -> Stats:

@@ -181,6 +181,50 @@ def simulate_smart_batch(z, y, thresh, eta0: float = SQRT2, *, lanes_per_seq: in
     return (reg, sw) if return_switch else reg
 
 
+def _thresholds(thresholds, B: int) -> np.ndarray:
+    """The switch thresholds of a sweep as a contiguous float64 array [B, M]: real numbers,
+    ``[M]`` (every sequence the same) or ``[B, M]`` (per sequence); any values (NaN and ±inf
+    included), any order, duplicates allowed.  Raises ValueError otherwise."""
+    try:
+        a = np.asarray(thresholds)
+    except Exception as e:  # ragged lists
+        raise ValueError(f"thresholds must be [M] or [B, M] real numbers: {e}") from None
+    if a.ndim not in (1, 2):
+        raise ValueError(f"thresholds must be [M] or [B, M], got shape {a.shape}")
+    if a.size and not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise ValueError(f"thresholds must be real numbers, got dtype {a.dtype}")
+    if a.ndim == 2 and a.shape[0] != B:
+        raise ValueError(f"per-sequence thresholds must be [B = {B}, M], got shape {a.shape}")
+    return np.array(np.broadcast_to(a, (B, a.shape[-1])), dtype=np.float64, order="C")
+
+
+def simulate_smart_thresholds_batch(z, y, thresholds, eta0: float = SQRT2, *,
+                                    lanes_per_seq: int = LANES_BEST, device: int = 0,
+                                    return_switch: bool = False):
+    """Threshold sweep: SMART (fast_algorithms.py:118-164) over B sequences for every switch
+    threshold of ``thresholds`` ([M], or [B, M] per sequence), each pass over z serving a
+    group of them (ocx_simulate_smart_thresholds_batch): one FTL trajectory, one prefix test
+    and one comparator per pass, a switch step and an FTRL state per column.
+
+    Column m is simulate_smart_batch's lane-group kernel with thresh = thresholds[..., m]: in
+    the bit-exact modes (lanes_per_seq 1 / -k) the reference's prefix re-scan and streamed
+    comparator, bit for bit; in the others both closed forms.  ``thresh = +inf`` makes a
+    column FTL's regret, with the same adds and the same comparator; ``sqrt(2T)`` and the
+    empirical g(T) are the drivers' SMART and EMP.  Returns regret [B, M] or, with
+    ``return_switch``, (regret, switch_step [B, M] int64, -1 = never)."""
+    z = _f64(z)
+    y = _f64(y)
+    B, T, d = _check_zy(z, y)
+    th = _thresholds(thresholds, B)
+    M = int(th.shape[1])
+    reg = np.zeros((B, M))
+    sw = np.full((B, M), -1, dtype=np.int64)
+    _lib.call("ocx_simulate_smart_thresholds_batch", ptr(z), ptr(y), B, T, d, ptr(th), M,
+              float(eta0), ptr(reg), sw.ctypes.data_as(_lib.c_i64p), int(lanes_per_seq),
+              int(device))
+    return (reg, sw) if return_switch else reg
+
+
 def replay_batch(z, y, actions, *, device: int = 0):
     """exact_ftl.py:306-333 over B sequences: actions [B, T+1, d] → (cum_loss, comp_loss)."""
     z = _f64(z)
@@ -720,6 +764,48 @@ class DeviceBatch:
                   stats.data_ptr() if stats is not None else None, self._sp)
         self._keep_th = self._hold(th)
         return self.regret
+
+    def simulate_smart_thresholds(self, thresholds, eta0: float = SQRT2, *,
+                                  closed_prefix: Optional[bool] = None,
+                                  closed_comparator: Optional[bool] = None, stats=None,
+                                  _group=None):
+        """Threshold sweep of the resident batch (ocx_dev_simulate_smart_thresholds, async):
+        SMART for every switch threshold of ``thresholds`` ([M], or [B, M] per sequence;
+        validated here, NaN and ±inf are legal), each pass over z serving
+        ocx_smart_thresholds_group(L, M) of them.  Returns device tensors ``regret`` [B, M]
+        float64 and ``switch_step`` [B, M] int64 (-1 = never); column m is what
+        simulate_smart(thresholds[..., m], eta0, stats=...) gives, bit for bit in the same
+        layout.  ``thresh = +inf`` makes a column FTL's regret, with the same adds and the same
+        comparator; ``sqrt(2T)`` and the empirical g(T) are the drivers' SMART and EMP.
+        ``closed_prefix`` / ``closed_comparator`` default as in simulate_smart; ``stats``
+        ([2] int64 device tensor, optional) accumulates, per pass, the (sequence, step) pairs
+        that re-scanned — once per step however many columns needed it — and the sequences
+        that took the closed comparator.  (``_group``: tests and tools/thresholds_probe.py
+        force the group size through include/ocx_testing.h.)"""
+        torch = self.torch
+        B = int(self.L.B)
+        tha = _thresholds(thresholds, B)
+        M = int(tha.shape[1])
+        if closed_prefix is None:
+            closed_prefix = not self.exact
+        if closed_comparator is None:
+            closed_comparator = not self.exact
+        flags = ((_lib.OCX_SMART_CLOSED_PREFIX if closed_prefix else 0) |
+                 (_lib.OCX_ALG_CLOSED_COMPARATOR if closed_comparator else 0))
+        with torch.cuda.device(self.device), self._on_stream():
+            th = torch.as_tensor(tha).to(self.device)
+            out = {"regret": torch.zeros((B, M), dtype=torch.float64, device=self.device),
+                   "switch_step": torch.full((B, M), -1, dtype=torch.int64, device=self.device)}
+        args = (self._lp(), self.z.data_ptr(), self.y.data_ptr(), th.data_ptr() if B * M else None,
+                M, float(eta0), out["regret"].data_ptr() if B * M else None,
+                out["switch_step"].data_ptr() if B * M else None, flags,
+                stats.data_ptr() if stats is not None else None)
+        if _group is None:
+            self._call("ocx_dev_simulate_smart_thresholds", *args, self._sp)
+        else:
+            self._call("ocx_test_simulate_smart_thresholds", *args, int(_group), self._sp)
+        self._keep_th = self._hold(th)
+        return out
 
     def simulate_twin32(self, algo: int = 0, eta0: float = SQRT2, thresh=None):
         """The float32 twin (algorithms.py; twin32_batch) on the resident batch, which must
