@@ -4,7 +4,8 @@
 // calls the pipelined pieces and ocx_loss_grad / ocx_cert_grad; the plain curve kernel and the
 // curve comparator kernel (ocx_alg_curve.hip) call ocx_plain_step, ocx_closed_comp,
 // ocx_comp_stream and OcxSeq.  Not users, their step stays written out: ocx_alg_kernel
-// (ocx_sim.hip), ocx_alg_chunk_kernel (ocx_stream.hip), ocx_smart_closed.hip — with any of
+// (ocx_sim.hip), ocx_alg_chunk_kernel (ocx_stream.hip), the SMART kernel's FTL leg
+// (ocx_smart_thresholds.hip; measured on its former single-threshold twin) — with any of
 // these pieces their machine code changes — and the step-size kernels (ocx_alg_etas.hip), which
 // measured slower built from them.  DESIGN.md §3.9, "Shared step", has the figures.
 //

@@ -117,17 +117,19 @@ hipError_t ocx_launch_exact_big(const double* z, const double* y, int64_t B, int
 hipError_t ocx_launch_smart(const ocx_layout* L, const double* zt, const double* yt,
                             const double* th, double eta0, double* reg, int64_t* sw,
                             hipStream_t st);
-// SMART in O(T·d) (ocx_smart_closed.hip): closed_prefix decides the switch from the
-// closed-form prefix loss outside a rounding guard band (re-scan inside it: the reference's
-// decisions); closed_comp takes the final comparator loss in closed form where certified.
+// SMART in lane-group form (ocx_smart_thresholds.hip, one kernel with 1, 2 or 4 threshold
+// columns): closed_prefix decides the switch from the closed-form prefix loss outside a
+// rounding guard band (re-scan inside it: the reference's decisions), O(T·d); closed_comp takes
+// the final comparator loss in closed form where certified.
 // stats (nullable, device [2]): += re-scanned steps, += sequences with the closed comparator
+// One threshold per sequence, th / reg / sw [B]: one launch of the one-column instance.
 hipError_t ocx_launch_smart_closed(const ocx_layout* L, const double* zt, const double* yt,
                                    const double* th, double eta0, double* reg, int64_t* sw,
                                    int closed_prefix, int closed_comp, unsigned long long* stats,
                                    hipStream_t st);
-// Threshold sweeps (ocx_smart_thresholds.hip): ocx_launch_smart_closed for the M thresholds
-// th [B][M] (device) in passes of at most `group` (1, 2 or 4; ocx_thresholds_instance)
-// columns; reg / sw [B][M] (sw nullable); stats per launch.  ocx_thresholds_best_group: the
+// Threshold sweeps: the M thresholds th [B][M] (device) in passes of at most `group` (1, 2 or
+// 4; ocx_thresholds_instance) columns, each column the bits of ocx_launch_smart_closed with
+// that threshold; reg / sw [B][M] (sw nullable); stats per launch.  ocx_thresholds_best_group: the
 // group the measurements chose.
 bool ocx_thresholds_instance(const ocx_layout* L, int group);
 int ocx_thresholds_best_group(const ocx_layout* L);

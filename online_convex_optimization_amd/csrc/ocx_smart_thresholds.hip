@@ -1,43 +1,76 @@
-// ocx_smart_thresholds.hip — SMART threshold sweeps: SMART (fast_algorithms.py:118-164) for
-// NT switch thresholds in one pass over z.
+// ocx_smart_thresholds.hip — SMART (fast_algorithms.py:118-164) in lane-group form, for NT
+// switch thresholds per pass over z: the single-threshold calls (ocx_launch_smart_closed) run
+// its one-column instance, the threshold sweeps (ocx_launch_smart_thresholds) 1, 2 or 4 columns.
 //
-// SMART's only parameter is the threshold at which it leaves FTL for FTRL, and almost all of
-// `_simulate_SMART_like_core` does not depend on it: the FTL leg (theta_ftl, its action,
-// ftl_loss, :140-146), the prefix loss s_loss of the switch test (:157-159) and the final
-// comparator FTL(theta_ftl) (:162-163).  What depends on it is the step at which
-// ftl_loss − s_loss >= thresh first holds, the FTRL state grown from that step on, and
-// total_loss — which before the switch is ftl_loss bit for bit (the same additions from 0).
+// Two modes.  closed_prefix = 0: the reference's re-scan at every pre-switch step.
+// closed_prefix = 1: O(T·d) per sequence, as follows.
 //
-// The kernel is the NT-column form of ocx_smart_closed_kernel (ocx_smart_closed.hip): the
-// same layouts, ring loads and dispatch, both of its modes (closed_prefix = 1: the O(T·d)
-// guarded closed form; closed_prefix = 0: the reference's re-scan at every pre-switch step).
+// The closed form of the prefix loss.  The reference's SMART re-scans the whole prefix before
+// the switch: at every step t it sums ½|z_i·s_t − y_i| over i = 0..t
+// (`_comparator_loss_prefix`, :79-85, called at :158), O(T²·d) per sequence, and compares
+// ftl_loss − s_loss with the threshold (:159).  On the reference's own data that prefix loss
+// has a closed form.  When every row so far lies in the unit ball (||z_i|| <= 1: the g(T)
+// sampler and the random families clip them) and every label is ±1, |z_i·s_t| <= 1 for the
+// unit-norm FTL action s_t, so ½|z_i·s_t − y_i| = ½(1 − y_i z_i·s_t) and
 //
-// One copy per sequence, operation for operation the parent's: tf, xf, sv, ftl_loss, regime,
-// clean, the z / y ring, and the comparator (streamed, or T/2 − ||theta_ftl|| where clean).
+//     s_loss_t = (t+1)/2 − ½ s_t·S_t,   S_t = Σ_{i<=t} y_i z_i,
+//
+// one dot product per step with S_t kept beside theta in registers.  The closed form differs
+// from the reference's sequential sum only by rounding, so it DECIDES the switch only where
+// ftl_loss − s_loss is farther from the threshold than a bound on that rounding (`guard`
+// below); inside the band, or once a row leaves the ball or a label is not ±1, the step
+// re-scans its prefix exactly as the reference does.  The switch step is therefore the
+// reference's (bit-identical decisions in the exact layouts), and the regret — total_loss
+// minus the comparator loss, both summed as the reference does — is unchanged.
+//
+// The guard band (u = 2^-53), four error terms:
+//  1. the reference's prefix sum differs from the exact value of Σ ½|z_i·s_t − y_i| by at most
+//     (t+1)·u·(t + d/2 + 2) (d-term dot products, t+1 ordered adds of terms <= 1);
+//  2. that value differs from the closed form's exact value by at most
+//     (t+1)·(5e-13 + (d/2 + 4)·u) (rows certified to ||z||² <= 1 + 1e-12, ||s_t|| <= 1 + a few u);
+//  3. the computed closed form differs from its exact value by at most (t+1)·u·(t + d + 1)
+//     (S_t's sums, the dot, the final subtraction);
+//  4. the decision's own subtractions add 2u·(|ftl_loss| + |s| + |thresh|).
+// The band is about twice their sum.  An infinite threshold must not widen it (+inf: never
+// fires, D = −inf; −inf: fires at once, D = +inf), and a NaN one never fires (`>= NaN` is
+// false, :159): both are decided in the band test, not by O(t) re-scans.
+//
+// The comparator.  The final comparator FTL(theta_ftl) (:162-163) is streamed as the
+// reference does, or — closed_comp, not in the bit-exact APIs — taken in closed form
+// T/2 − ||theta_ftl|| where every FTL sub-gradient was −y_t/2 (then theta_ftl = −½ S_T; see
+// ocx_alg_kernel's onepass comparator), which makes the whole kernel one HBM pass.
+//
+// What the columns share.  SMART's only parameter is the threshold at which it leaves FTL for
+// FTRL, and almost all of `_simulate_SMART_like_core` does not depend on it: the FTL leg
+// (theta_ftl, its action, ftl_loss, :140-146), the prefix loss s_loss of the switch test
+// (:157-159) and the final comparator.  So there is one copy per sequence of tf, xf, sv,
+// ftl_loss, regime, clean, the z / y ring, and the comparator.  What depends on the threshold
+// is the step at which ftl_loss − s_loss >= thresh first holds, the FTRL state grown from that
+// step on, and total_loss — which before the switch is ftl_loss bit for bit (the same
+// additions from 0).
 //
 // Per column m: switched[m], sw[m], tr[m][C] and total[m].  An unswitched column keeps no
 // total of its own: it is ftl_loss, copied at the switch step after that step's add (the
-// parent adds the step's FTL loss to total_loss before it tests, :156).  After the switch the
-// column takes the parent's FTRL step with the global t.  The FTRL steps of the columns of a
-// sequence run side by side under one branch (some column of the sequence has switched) and
-// are committed per column, so that the NT independent chains interleave; a column that has
-// not switched runs on theta = 0 and commits nothing.
+// reference adds the step's FTL loss to total_loss before it tests, :156).  After the switch
+// the column takes the FTRL step with its own theta and the global t (:148-154).  The FTRL
+// steps of the columns of a sequence run side by side under one branch (some column of the
+// sequence has switched) and are committed per column, so that the NT independent chains
+// interleave; a column that has not switched runs on theta = 0 and commits nothing.
 //
 // The switch test runs while some column of the sequence is unswitched.  The shortcut
 // ftl_loss < th_m is per column; the closed form s_cl and ftl_loss − s_cl are formed once and
-// D_m = (ftl_loss − s_cl) − th_m is the parent's left-to-right order; the guard takes that
-// column's |th_m|, with the parent's NaN and ±inf handling.  If any column is left undecided
-// the prefix is re-scanned ONCE, exactly as the parent does, and every still-undecided column
-// of that step is decided by the reference's ftl_loss − s_loss >= th_m: s_loss does not
-// depend on the threshold.  Every decision is the one the parent takes with thresh = th_m, so
-// each column's switch step, and with it every bit of its regret, is the parent's.
+// D_m = (ftl_loss − s_cl) − th_m is taken left to right; the guard takes that column's
+// |th_m|.  If any column is left undecided the prefix is re-scanned ONCE and every
+// still-undecided column of that step is decided by the reference's
+// ftl_loss − s_loss >= th_m: s_loss does not depend on the threshold.  A column's decisions,
+// and with them its switch step and every bit of its regret, do not depend on which other
+// columns share its pass.
 //
-// Cross-lane rules (the parent's): the row certification and the comparator ballots see the
-// whole wave; the re-scan and the FTRL branch are uniform per lane group (they depend on the
-// sequence's state only).  Padding sequences (b >= B) start with every column switched and
-// read no threshold.
+// Cross-lane rules: the row certification and the comparator ballots see the whole wave; the
+// re-scan and the FTRL branch are uniform per lane group (they depend on the sequence's state
+// only).  Padding sequences (b >= B) start with every column switched and read no threshold.
 //
-// Thresholds are a device array [B][M] (per-sequence thresholds, like thresh[B] of the
+// Thresholds are a device array [B][M] (per-sequence thresholds; M = 1 for the
 // single-threshold calls); outputs regret [B][M] and switch_step [B][M], this launch's columns
 // m0 … m0 + nt − 1.  A launch may hold fewer columns than its instance (nt < NT: 3 of 4): the
 // spare column runs on a copy of the last threshold and writes nothing.  stats[0] counts
@@ -204,7 +237,7 @@ __global__ __launch_bounds__(OCX_BLOCK) void ocx_smart_thresholds_kernel(ThreshA
                             if (und[m]) {
                                 const double D = Dl - th[m];
                                 // an infinite threshold must not widen the band, and a NaN
-                                // one never fires (ocx_smart_closed_kernel)
+                                // one never fires (header, the guard band)
                                 const double tha = __builtin_isfinite(th[m]) ? fabs(th[m]) : 0.0;
                                 const double guard = gbase + 4e-16 * (fabs(ftl_loss) + n1 + tha);
                                 if (th[m] != th[m]) {
@@ -306,14 +339,14 @@ constexpr bool thresh_instance(int C, int NT) {
     return NT == 1 || (NT == 2 && C <= 16) || (NT == 4 && C <= 8);
 }
 
-// Ring depth: the parent's, except for the long exact chains with several columns, as in
-// the step-size sweep (etas_nb, ocx_alg_etas.hip): NT copies of the chain code in each of the
-// parent's ring slots pass the compiler's unroll budget, and the ring then stays a
-// dynamically indexed array in scratch where the parent has none (8 x 16 chained, four
-// columns: 272 B per lane).  One lane with 32 coordinates or more (its four state vectors alone
-// pass the register file, parent and sweep both spill) loads each row where it is used, a ring
-// of one: at the parent's two this kernel spilled 40 to 270 B per lane more than the parent,
-// at one it spills less.  The ring depth is no part of the arithmetic.
+// Ring depth: nb_for's (the FTRL/FTL kernels'), except for the long exact chains with several
+// columns, as in the step-size sweep (etas_nb, ocx_alg_etas.hip): NT copies of the chain code
+// in each of nb_for's ring slots pass the compiler's unroll budget, and the ring then stays a
+// dynamically indexed array in scratch where one column has none (8 x 16 chained, four
+// columns: 272 B per lane).  One lane with 32 coordinates or more (its state vectors alone
+// pass the register file, every instance spills) loads each row where it is used, a ring of
+// one: at nb_for's two the one-column instance spilled 512 to 2832 B per lane, at one it
+// spills 0 to 2036.  The ring depth is no part of the arithmetic.
 constexpr int thresh_nb(int C, int P, bool CHAIN, int NT) {
     const int nb = nb_for(C, P, false);
     if (P == 1 && C >= 32) return 1;
@@ -362,7 +395,7 @@ bool ocx_thresholds_instance(const ocx_layout* L, int group) {
 }
 
 // The dispatcher's group rule.  Measured (profiles/thresholds_ab.jsonl) with
-// both closed forms against M calls of the existing single-threshold kernel on the same
+// both closed forms against M single-threshold calls (then a kernel of their own) on the same
 // resident data, in every class of loop form (chained short and long, butterfly of 8 lanes or
 // more, butterfly of fewer lanes, one lane) x coordinates per lane: the largest instantiated
 // group was the fastest (0.55-0.61x of the loop at M = 4 up to 8 coordinates per lane,
@@ -376,27 +409,26 @@ int ocx_thresholds_best_group(const ocx_layout* L) {
     return (L->C == 8 && !L->chain && L->P >= 8) ? 2 : 4;
 }
 
+// One threshold per sequence: th, reg, sw [B] read as [B][1], one launch of the one-column
+// instance.
+hipError_t ocx_launch_smart_closed(const ocx_layout* L, const double* zt, const double* yt,
+                                   const double* th, double eta0, double* reg, int64_t* sw,
+                                   int closed_prefix, int closed_comp, unsigned long long* stats,
+                                   hipStream_t st) {
+    if (L->G == 0) return hipSuccess;
+    const ThreshArgs a{zt, yt, L->B, L->T, L->d, L->G, th, /*M*/ 1, /*m0*/ 0, /*nt*/ 1,
+                       eta0, reg, sw, closed_prefix, closed_comp, stats};
+    OCX_DISPATCH(launch_thresh1_cp, L, a, st)
+}
+
 hipError_t ocx_launch_smart_thresholds(const ocx_layout* L, const double* zt, const double* yt,
                                        const double* th, int64_t M, double eta0, double* reg,
                                        int64_t* sw, int closed_prefix, int closed_comp,
                                        unsigned long long* stats, int group, hipStream_t st) {
     if (L->G == 0 || M <= 0) return hipSuccess;
     if (!ocx_thresholds_instance(L, group)) return hipErrorInvalidValue;
-    ThreshArgs a{};
-    a.zt = zt;
-    a.yt = yt;
-    a.B = L->B;
-    a.T = L->T;
-    a.d = L->d;
-    a.G = L->G;
-    a.thresh = th;
-    a.M = M;
-    a.eta0 = eta0;
-    a.regret = reg;
-    a.switch_step = sw;
-    a.closed_prefix = closed_prefix;
-    a.closed_comp = closed_comp;
-    a.stats = stats;
+    ThreshArgs a{zt, yt, L->B, L->T, L->d, L->G, th, M, /*m0*/ 0, /*nt*/ 0,
+                 eta0, reg, sw, closed_prefix, closed_comp, stats};  // m0, nt: per launch
     for (int64_t m0 = 0; m0 < M; m0 += group) {
         const int nt = (int)(M - m0 < group ? M - m0 : group);
         const int NT = nt <= 1 ? 1 : (nt <= 2 ? 2 : 4);  // the smallest instance that holds them

@@ -1,17 +1,23 @@
-"""GPU: SMART in O(T·d) (csrc/ocx_smart_closed.hip, ocx_dev_simulate_smart_ex).
+"""GPU: SMART in O(T·d) (ocx_dev_simulate_smart_ex: the one-column instance of the lane-group
+kernel in csrc/ocx_smart_thresholds.hip, which the threshold sweeps run with more columns).
 
 The pre-switch prefix loss of fast_algorithms.py:157-160 has the closed form
 (t+1)/2 − ½ s_t·S_t on clipped rows with ±1 labels; the kernel lets it decide the switch
 only outside a rounding guard band and re-scans the prefix inside it, so its switch steps
 must be the reference's: bit-identical regrets whenever the final comparator keeps the
 reference's streamed sum (OCX_SMART_CLOSED_PREFIX alone), close_closed with the
-closed-form comparator (the batched default outside the bit-exact modes)."""
+closed-form comparator (the batched default outside the bit-exact modes).
+
+The last test pins the call's bits in every layout of the sweep tests to a record taken
+before the single-threshold kernel and the sweep kernel were merged
+(tests/golden/smart_single_bits.json, tests/_smart_bits.py)."""
 import math
 
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import _smart_bits as SB
 from tests._golden import F
 from tests.test_gpu_parity import PUBLISHED_GT, close_closed
 
@@ -175,3 +181,39 @@ def test_non_finite_thresholds_decide_without_rescan(eng):
         z, y = O.gT_sample(5, T, b, d)
         ref, rsw = O.simulate_SMART_like(z, y, float(th[b]), SQ2, return_switch=True)
         assert reg[b] == ref and sw[b] == rsw, (b, reg[b], ref, sw[b], rsw)
+
+
+@pytest.fixture(scope="module")
+def record():
+    return SB.load()
+
+
+def test_the_record_holds_every_case(record):
+    assert set(record["cases"]) == {SB.case_id(P, d, name) for P, d in SB.LAYOUTS
+                                    for name in SB.FAMILIES}
+    assert len(SB.LAYOUTS) == 17 and len(record["cases"]) == 34
+
+
+@pytest.mark.parametrize("name", SB.FAMILIES)
+@pytest.mark.parametrize("P,d", SB.LAYOUTS)
+def test_single_threshold_bits_equal_the_record(eng, record, P, d, name):
+    """The lane-group call with one threshold per sequence (a stats tensor keeps flags 0 on
+    it too) against tests/golden/smart_single_bits.json, taken from the last commit where
+    that call was a kernel of its own: the same regret bits, switch steps and stats counters
+    for every flag pair and every recorded threshold, in every layout of the sweep tests.
+    With a closed form on, nothing else carries a butterfly layout's bits
+    (tests/_smart_bits.py)."""
+    want = record["cases"][SB.case_id(P, d, name)]
+    have = SB.inputs_digest(SB.C.family(name, d))
+    assert have == want["inputs"], \
+        f"inputs of family {name} at d = {d} are not the recorded ones: {have} != {want['inputs']}"
+    got = SB.run(eng, P, d, name)
+    assert got["layout"] == want["layout"], (P, d)
+    assert set(got["runs"]) == set(want["runs"]) and len(want["runs"]) == 3
+    for flags, cols in want["runs"].items():
+        assert set(got["runs"][flags]) == set(cols) and len(cols) == 7, flags
+        for th, (reg, sw, rescans, closed) in cols.items():
+            g = got["runs"][flags][th]
+            assert g[1] == sw, (P, d, name, flags, th, "switch_step")
+            assert g[0] == reg, (P, d, name, flags, th, "regret")
+            assert g[2:] == [rescans, closed], (P, d, name, flags, th, "stats", g[2:])

@@ -1,10 +1,14 @@
 """Threshold sweeps (ocx_dev_simulate_smart_thresholds and the layers above it): SMART for M
 switch thresholds in passes over z that each serve a group of them.
 
-The reference of every check is the C oracle or the existing single-threshold calls, never the
-sweep code: bit for bit against the oracle in the exact modes, bit for bit per column against
+Bit for bit against the C oracle in the exact modes, and bit for bit per column against
 DeviceBatch.simulate_smart on the same packed batch for every forced group size and every
-flag pair.  TH7 on the `beam` and `gt_like` rows (tests/_thresholds_cases.py, conditions
+flag pair.  That single-threshold call is the sweep kernel's own one-column instance (one
+launch, [B] read as [B][1]), so against group 1 the comparison checks the wrapper's strides
+and against groups 2 and 4 that a column's bits do not depend on its neighbours; what pins the
+one-column bits themselves is the oracle in the exact modes, the plain re-scan kernel in
+lane-group form (flags 0, every layout) and the record of tests/test_gpu_smart.py.  TH7 on
+the `beam` and `gt_like` rows (tests/_thresholds_cases.py, conditions
 asserted in tests/test_thresholds_cpu.py) gives every column of every sequence its own switch
 step and FTRL trajectory."""
 import ctypes
@@ -44,12 +48,14 @@ def new_stats(db):
 
 
 def single(db, th, pf, cc, stats=True):
-    """(regret [B], switch_step [B], stats [2]) of the existing single-threshold call on the
-    packed batch; th scalar or [B].  With a stats tensor the call runs the lane-group kernel
-    in the batch's own layout (ocx_smart_closed_kernel, the sweep's parent) for every flag
-    pair; without one, flags (False, False) go to ocx_dev_simulate_smart's dispatch, which at
-    d <= 64 is the one-wave-per-sequence kernel: it sums in the reference's order whatever
-    the layout, so it carries a butterfly layout's bits only in the exact modes."""
+    """(regret [B], switch_step [B], stats [2]) of the single-threshold call on the packed
+    batch; th scalar or [B].  With a stats tensor the call runs the lane-group kernel in the
+    batch's own layout for every flag pair: one launch of the sweep kernel's one-column
+    instance, thresholds and outputs [B] read as [B][1].  Without one, flags (False, False)
+    go to ocx_dev_simulate_smart's dispatch, other kernels: the plain re-scan kernel in
+    lane-group form (ocx_smart_kernel; always, under OCX_SMART_KERNEL=lanes), or at d <= 64
+    the one-wave-per-sequence kernel, which sums in the reference's order whatever the
+    layout, so it carries a butterfly layout's bits only in the exact modes."""
     import torch
     Bn = int(db.L.B)
     sw = torch.full((Bn,), -7, dtype=torch.int64, device=db.device)
@@ -101,7 +107,7 @@ FLAG_PAIRS = [(False, False), (True, False), (True, True)]
 
 @pytest.mark.parametrize("name", C.FAMILIES)
 @pytest.mark.parametrize("P,d", LAYOUTS)
-def test_columns_equal_the_existing_kernel_for_every_group(eng, P, d, name):
+def test_columns_equal_the_existing_kernel_for_every_group(eng, monkeypatch, P, d, name):
     from online_convex_optimization_amd import _lib
     f = C.family(name, d)
     db = eng.DeviceBatch(B, T, d, lanes_per_seq=P).pack(f.z, f.y)
@@ -115,7 +121,18 @@ def test_columns_equal_the_existing_kernel_for_every_group(eng, P, d, name):
             plain_reg, plain_sw, _ = existing(db, TH7, pf, cc, stats=False)
             assert np.array_equal(plain_sw, ref_sw), (P, d, name, pf, cc)
             assert np.array_equal(plain_reg, ref_reg), (P, d, name, pf, cc)
+        if not (pf or cc):
+            # an independent witness in every layout: the plain re-scan kernel in lane-group
+            # form (ocx_smart_kernel, ocx_sim.hip) shares no kernel code with the sweep
+            with monkeypatch.context() as mp:
+                mp.setenv("OCX_SMART_KERNEL", "lanes")   # read at every call
+                wit_reg, wit_sw, _ = existing(db, TH7, False, False, stats=False)
+            assert np.array_equal(wit_sw, ref_sw), (P, d, name, "lane-group witness")
+            assert np.array_equal(wit_reg, ref_reg), (P, d, name, "lane-group witness")
         ok = []
+        # group 1 against ref compares the one-column instance with itself: it still checks
+        # the wrapper's strides; groups 2 and 4, the oracle tests and the record of
+        # tests/test_gpu_smart.py carry the weight
         for group in (1, 2, 4):
             try:
                 got = host(db.simulate_smart_thresholds(TH7, SQ2, closed_prefix=pf,

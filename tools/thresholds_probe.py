@@ -1,6 +1,6 @@
 """Threshold sweep timing probe: what M switch thresholds cost through
-simulate_smart_thresholds, for every forced group size, next to M separate calls of the
-existing simulate_smart on the same resident data.  One JSON line per case, appended to
+simulate_smart_thresholds, for every forced group size, next to M separate calls of
+simulate_smart on the same resident data.  One JSON line per case, appended to
 profiles/thresholds_ab.jsonl (or --out).
 
   (a) generate_gT batches 32 768 x 1e3 x 5 and 32 768 x 1e3 x 64 (OCX_LANES_BEST), both closed
@@ -11,7 +11,13 @@ profiles/thresholds_ab.jsonl (or --out).
   (c) M in {2, 4} on further members of the dispatcher's classes (loop form x coordinates per
       lane), see main().
 
-The baseline is always the existing code, never the sweep code.  Thresholds are sqrt(2T) and
+The committed records were taken when simulate_smart() with the closed forms ran a
+single-threshold kernel of its own: there the baseline was the existing code, never the sweep
+code.  That call is now one launch of the sweep kernel's one-column instance, so in cases (a)
+and (c) the "loop" side runs the same kernel as group 1 and their ratio measures the sweep
+wrapper's host path only (tools/smart_single_probe.py has the single call across the merge);
+the committed records stay as the evidence of that earlier commit.  In case (b) the loop side
+is still another kernel.  Thresholds are sqrt(2T) and
 fractions of it, so the switches are spread over the horizon.  One process; device events on
 the batch's stream around every repetition; every shape warmed up; the sides of a comparison
 alternate repetition by repetition, so both see the same neighbours on the machine.  The
