@@ -49,6 +49,18 @@ int ocx_test_alg_range(const ocx_layout* L, const double* z_tiled, const double*
                        double eta0, int onepass, int64_t g0, int64_t gn, double* regret,
                        double* gmax, void* stream);
 
+/* The pipelined FTRL (ftl = 0) / FTL (ftl = 1) kernel's persistent instance — the one a batch
+ * of more wave-groups than are resident at once launches, each wave looping over groups w,
+ * w + nwaves, ... — on a resident batch of any size, with the number of waves forced to
+ * `nwaves` (>= 1), so a test reaches one wave running every group, uneven shares and more
+ * waves than groups.  onepass as in ocx_test_alg_range.  regret, cum, comp [B] doubles and
+ * closed_out [B] int32 (device; all but regret nullable): bit-identical to
+ * ocx_dev_simulate_alg_ex on the same data.  OCX_E_UNSUPPORTED for layouts without a
+ * persistent instance (it exists for 8 x 8).  Synchronises `stream`. */
+int ocx_test_alg_pipe_persistent(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                                 int ftl, double eta0, int onepass, int64_t nwaves, double* regret,
+                                 double* cum, double* comp, int32_t* closed_out, void* stream);
+
 /* ocx_dev_simulate_alg_etas with the group size forced to `group` (1, 2 or 4) instead of
  * ocx_etas_group's choice, so a test reaches every instantiated form whatever the dispatcher
  * prefers.  OCX_E_UNSUPPORTED where that form is not instantiated for the layout (group 2

@@ -134,6 +134,8 @@ TEST_SIGNATURES = {
                                           c_vp, c_vp, c_vp]),
     "ocx_test_alg_range": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_double, c_int, c_i64,
                                    c_i64, c_vp, c_vp, c_vp]),
+    "ocx_test_alg_pipe_persistent": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_int, c_double,
+                                             c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "ocx_test_simulate_alg_etas": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_dp, c_i64, c_vp,
                                            c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
     "ocx_test_simulate_smart_thresholds": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_vp, c_i64,

@@ -51,6 +51,7 @@ struct PipeArgs {
     int* closed_out;
     int onepass;
     int64_t g0, gn;  // wave-groups [g0, g0 + gn) of the layout
+    int64_t gstride; // persistent launches (alg_pipe_body, LOOP): the waves launched
     int64_t t0, tn;  // steps [t0, t0 + tn) (a whole run: 0, T)
     double* state;   // chunked runs: the carried state (nullable: whole run)
     int* bad;        // chunked runs: set when a sequence needs the second pass
@@ -72,8 +73,11 @@ struct PipeNoObserver {};
 // RT (FTRL): the rescale's sqrt only in waves where a sequence may need the rescale (see the
 // step).  CHUNK: a chunked run (t0, tn, state); the whole-run kernels compile without it, so
 // its bookkeeping costs them no registers (the lean form spilled with it: 148 B per lane).
-template <int C, int P, int NB, bool FTL, bool RT, bool CHUNK = false, class Obs = PipeNoObserver>
-__device__ __forceinline__ void alg_pipe_body(const PipeArgs& a, Obs&& obs = Obs{}) {
+// One wave-group's run: group wv (wave-uniform) of the launch's gn.  Every piece of state is
+// local to the call, so a wave that runs several groups (alg_pipe_body, LOOP) starts each from
+// scratch: the ring is filled again (one load latency per group) and nothing is carried over.
+template <int C, int P, int NB, bool FTL, bool RT, bool CHUNK, class Obs>
+__device__ __forceinline__ void alg_pipe_group(const PipeArgs& a, const int64_t wv, Obs& obs) {
     static_assert(P >= 2 && NB >= 4, "butterfly layouts, a ring holding z_{t-1} .. z_{t+1}");
     constexpr bool OBS = !std::is_same<typename std::decay<Obs>::type, PipeNoObserver>::value;
     using IT = pipe_step_t<C>;
@@ -81,10 +85,6 @@ __device__ __forceinline__ void alg_pipe_body(const PipeArgs& a, Obs&& obs = Obs
     constexpr int K = C / 2;
     constexpr int NS = pipe_state_words(C);
     const int lane = threadIdx.x & 63;
-    // wave-uniform, provably (readfirstlane): the tile bases live in SGPRs and every load
-    // is an SGPR base + the lane's constant offset, with no per-load address arithmetic
-    const int64_t wv = (int64_t)__builtin_amdgcn_readfirstlane((int)ocx_pipe_wave_id(a.gn));
-    if (wv >= a.gn) return;
     const int64_t g = a.g0 + wv;
     const int64_t T = a.T, t0 = CHUNK ? a.t0 : 0, tn = CHUNK ? a.tn : T;
     const bool first = !CHUNK || t0 == 0, last = !CHUNK || t0 + tn >= T;
@@ -264,6 +264,28 @@ __device__ __forceinline__ void alg_pipe_body(const PipeArgs& a, Obs&& obs = Obs
     }
 }
 
+// Which groups a wave runs.  Without LOOP: its one group (ocx_pipe_wave_id; a spare slot
+// leaves).  With LOOP (the persistent launch, launch_pipe_cp): wave w of the a.gstride launched
+// runs groups w, w + gstride, ... < gn, one after the other — a plain loop, no hand-off between
+// waves; a wave beyond gstride (the last block's spare slots) leaves.
+template <int C, int P, int NB, bool FTL, bool RT, bool CHUNK = false, class Obs = PipeNoObserver,
+          bool LOOP = false>
+__device__ __forceinline__ void alg_pipe_body(const PipeArgs& a, Obs&& obs = Obs{}) {
+    // wave-uniform, provably (readfirstlane): the tile bases live in SGPRs and every load
+    // is an SGPR base + the lane's constant offset, with no per-load address arithmetic
+    if constexpr (!LOOP) {
+        const int64_t wv = (int64_t)__builtin_amdgcn_readfirstlane((int)ocx_pipe_wave_id(a.gn));
+        if (wv >= a.gn) return;
+        alg_pipe_group<C, P, NB, FTL, RT, CHUNK>(a, wv, obs);
+    } else {
+        static_assert(!CHUNK, "a chunked run carries one group's state per wave");
+        const int64_t w0 = (int64_t)__builtin_amdgcn_readfirstlane((int)ocx_wave_id());
+        if (w0 >= a.gstride) return;
+        for (int64_t wv = w0; wv < a.gn; wv += a.gstride)
+            alg_pipe_group<C, P, NB, FTL, RT, CHUNK>(a, wv, obs);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Launch policy of the pipelined kernels (host)
 // ---------------------------------------------------------------------------
@@ -288,11 +310,14 @@ inline bool ocx_alg_use_pipe(const ocx_layout* L) {
     return !no_pipe && ocx_pipe_supported(L);
 }
 
-// Waves per block of the full-form launch: four (one wave per SIMD of a CU, the last blocks
-// three, ocx_pipe_wave_id) unless OCX_BLOCK_WAVES forces another shape or the launch has
-// fewer than four groups.  The few-wave batches measured one-wave blocks (which the plain
-// kernels keep below eight waves per CU) slower: profiles/r04_pipe_bw_ab.jsonl,
-// r04_wave_clock*.jsonl.
+// Waves per block of the full-form launch: four (a block spreads one wave to each SIMD of its
+// CU, the last blocks three, ocx_pipe_wave_id) unless OCX_BLOCK_WAVES forces another shape or
+// the launch has fewer than four groups.  That is the block's shape, not the residency: the
+// 8 x 8 full form compiles to 212 VGPRs, two waves per SIMD, so a CU holds two such blocks and
+// a launch of more than 2 x 4 x CUs groups would run in dispatcher rounds — such a batch takes
+// the persistent launch instead (ocx_alg_pipe.hip, launch_pipe_cp).  The few-wave batches
+// measured one-wave blocks (which the plain kernels keep below eight waves per CU) slower:
+// profiles/r04_pipe_bw_ab.jsonl, r04_wave_clock*.jsonl.
 inline int pipe_block_waves(int64_t G) {
     if (std::getenv("OCX_BLOCK_WAVES")) return ocx_block_waves(G);
     return G >= 4 ? 4 : 1;

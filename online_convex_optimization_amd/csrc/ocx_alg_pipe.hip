@@ -36,21 +36,153 @@
 // the second comparator pass: a sequence the closed form cannot certify gets a NaN regret
 // and raises *bad (the caller runs its batch again in the sequential path).
 #include <cmath>
+#include <map>
+#include <mutex>
 
 #include "ocx_alg_pipe.h"
 #include "ocx_device_math.h"
 #include "ocx_internal.h"
 #include "ocx_sim_kernels.h"
 
-template <int C, int P, int NB, bool FTL, int MINW = 1, bool CHUNK = false>
+template <int C, int P, int NB, bool FTL, int MINW = 1, bool CHUNK = false, bool LOOP = false>
 __global__ __launch_bounds__(OCX_BLOCK, MINW) void ocx_alg_pipe_kernel(PipeArgs a) {
-    alg_pipe_body<C, P, NB, FTL, pipe_rt<C, P, MINW>(), CHUNK>(a);
+    alg_pipe_body<C, P, NB, FTL, pipe_rt<C, P, MINW>(), CHUNK, PipeNoObserver, LOOP>(a);
+}
+
+// ---------------------------------------------------------------------------
+// The persistent launch: a batch of more groups than are resident at once
+// ---------------------------------------------------------------------------
+// The full form compiles to 212 VGPRs at 8 x 8 (two waves per SIMD), so a launch of more
+// than 2 x 4 x CUs groups runs in dispatcher rounds, each wave with NB − 2 steps of loads in
+// flight: 4 096 groups are two rounds of 2 048 waves x 7 steps, ≈60 MB outstanding where
+// latency x bandwidth needs ≈8.6 MB.  Such a batch instead launches OCX_PIPE_PERS_WPS waves
+// per SIMD of an instance with a ring of OCX_PIPE_PERS_NB slots, once, and every wave loops
+// over its share of the groups (alg_pipe_body, LOOP).  Four-wave blocks, one wave per SIMD;
+// where the instance's registers admit more blocks per CU than wanted, a dynamic-LDS request
+// the kernel never touches caps them, so no CU takes two blocks while another takes none.
+// Measured at the bench batch (profiles/persistent_sweep.jsonl): what counts
+// is the residency — one wave per SIMD 26.06–26.13 ms at every ring depth tried (2, 3, 4, 7
+// steps in flight), two per SIMD 26.41–26.45 ms, the two-round launch 26.48–26.51 ms — so the
+// shipped point is one wave per SIMD with the shortest ring.  Under a 128-VGPR budget
+// (MINW = 4) the looped form spills (24 B per lane at 4 slots), so the instance takes the
+// 256-VGPR budget: 132 VGPRs, no scratch.  8 x 8 only: the layout of the d = 64 batches
+// large enough to get here; FTRL and FTL alike (25.94 -> 25.32 ms for FTL,
+// profiles/persistent_pipe_lib_ab.jsonl).
+#ifndef OCX_PIPE_PERS_NB
+#define OCX_PIPE_PERS_NB 4
+#endif
+#ifndef OCX_PIPE_PERS_MINW  // the instance's register budget: 512 / MINW VGPRs
+#define OCX_PIPE_PERS_MINW 2
+#endif
+#ifndef OCX_PIPE_PERS_WPS
+#define OCX_PIPE_PERS_WPS 1
+#endif
+#ifndef OCX_PIPE_PERS_TUNE  // tuning builds (tools/persistent_sweep.py): the launch shape from
+#define OCX_PIPE_PERS_TUNE 0  // OCX_PIPE_PERS_WPS / OCX_PIPE_PERS_BW in the environment, per launch
+#endif
+
+template <int C, int P>
+constexpr bool pipe_persistent_layout() {
+    return C == 8 && P == 8;
 }
 
 namespace {
+struct PersGeom {
+    hipError_t err = hipSuccess;
+    int64_t round = 0;  // waves of the one-group-per-wave instance resident at once
+    int64_t nw = 0;     // waves the persistent launch starts
+    size_t lds = 0;     // its dynamic-LDS request (the cap on blocks per CU)
+};
+
+// Blocks of bw waves per CU so that `wps` waves sit on each SIMD, and the LDS request that
+// keeps the dispatcher to that many.
+template <class K>
+hipError_t pers_shape(K kern, int dev, int cus, int wps, int bw, PersGeom& gm) {
+    const int want = wps * 4 / bw;
+    int lds_cu = 0, q = 0;
+    if (hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) !=
+            hipSuccess || lds_cu <= 0)
+        lds_cu = 160 * 1024;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kern, 64 * bw, 0);
+    if (e != hipSuccess) return e;
+    size_t lds = 0;
+    if (q > want) {
+        for (lds = ((size_t)lds_cu / (want + 1) / 512 + 1) * 512; lds <= (size_t)lds_cu; lds += 512) {
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kern, 64 * bw, lds);
+            if (e != hipSuccess) return e;
+            if (q <= want) break;
+        }
+    }
+    if (q <= 0 || q > want) return hipErrorInvalidConfiguration;
+    gm.lds = lds;
+    gm.nw = (int64_t)q * bw * cus;
+    return hipSuccess;
+}
+
+template <int C, int P>
+PersGeom pers_geometry(int ftl) {
+    constexpr int NB = pipe_nb<C>(P), NBP = OCX_PIPE_PERS_NB, MW = OCX_PIPE_PERS_MINW;
+    PersGeom gm;
+    int dev = 0, cus = 0;
+    if ((gm.err = hipGetDevice(&dev)) != hipSuccess) return gm;
+    int wps = OCX_PIPE_PERS_WPS, bw = 4;
+#if OCX_PIPE_PERS_TUNE
+    if (const char* e = std::getenv("OCX_PIPE_PERS_WPS")) wps = std::atoi(e);
+    if (const char* e = std::getenv("OCX_PIPE_PERS_BW")) bw = std::atoi(e);
+    if (wps < 1 || wps > 8 || (bw != 1 && bw != 4)) return gm.err = hipErrorInvalidValue, gm;
+#else
+    static std::mutex mu;
+    static std::map<std::pair<int, int>, PersGeom> cache;
+    std::lock_guard<std::mutex> lk(mu);
+    const auto key = std::make_pair(dev, ftl);
+    const auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+#endif
+    if ((gm.err = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess)
+        return gm;
+    int q = 0;
+    gm.err = ftl ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, ocx_alg_pipe_kernel<C, P, NB, true>, 256, 0)
+                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, ocx_alg_pipe_kernel<C, P, NB, false>, 256, 0);
+    if (gm.err != hipSuccess) return gm;
+    gm.round = (int64_t)q * 4 * cus;
+    gm.err = ftl ? pers_shape(ocx_alg_pipe_kernel<C, P, NBP, true, MW, false, true>, dev, cus, wps, bw, gm)
+                 : pers_shape(ocx_alg_pipe_kernel<C, P, NBP, false, MW, false, true>, dev, cus, wps, bw, gm);
+#if !OCX_PIPE_PERS_TUNE
+    if (gm.err == hipSuccess) cache.emplace(key, gm);
+#endif
+    return gm;
+}
+
+// nwaves > 0 (ocx_test_alg_pipe_persistent): that many waves instead of the geometry's
+template <int C, int P>
+hipError_t launch_pipe_persistent(PipeArgs a, int ftl, int64_t nwaves, const PersGeom& gm,
+                                  hipStream_t st) {
+    constexpr int NBP = OCX_PIPE_PERS_NB, MW = OCX_PIPE_PERS_MINW;
+    int bw = 4;
+#if OCX_PIPE_PERS_TUNE
+    if (const char* e = std::getenv("OCX_PIPE_PERS_BW")) bw = std::atoi(e) == 1 ? 1 : 4;
+#endif
+    a.gstride = nwaves > 0 ? nwaves : gm.nw;
+    const dim3 grid = ocx_grid(a.gstride, bw), block(64 * bw);
+    if (ftl)
+        hipLaunchKernelGGL((ocx_alg_pipe_kernel<C, P, NBP, true, MW, false, true>), grid, block, gm.lds, st, a);
+    else
+        hipLaunchKernelGGL((ocx_alg_pipe_kernel<C, P, NBP, false, MW, false, true>), grid, block, gm.lds, st, a);
+    return hipGetLastError();
+}
+
 template <int C, int P>
 hipError_t launch_pipe_cp(const PipeArgs& a, int ftl, hipStream_t st) {
     constexpr int NB = pipe_nb<C>(P);
+    if constexpr (pipe_persistent_layout<C, P>()) {
+        // more groups than one round holds; every smaller batch (the few-wave T = 1e5 shapes,
+        // the capacity-limited ones) keeps its one-group-per-wave launch below
+        if (!a.state) {
+            const PersGeom gm = pers_geometry<C, P>(ftl);
+            if (gm.err != hipSuccess) return gm.err;
+            if (a.gn > gm.round) return launch_pipe_persistent<C, P>(a, ftl, 0, gm, st);
+        }
+    }
     const int bw = pipe_block_waves(a.gn);
     const dim3 grid = ocx_grid(a.gn, bw), block(64 * bw);
     if (a.state)  // a chunked run (FTRL: the trailing pipeline's algorithm)
@@ -85,6 +217,7 @@ PipeArgs pipe_args(const ocx_layout* L, const double* zt, const double* yt, doub
     a.onepass = onepass;
     a.g0 = 0;
     a.gn = L->G;
+    a.gstride = L->G;
     a.t0 = 0;
     a.tn = L->T;
     return a;
@@ -101,6 +234,24 @@ hipError_t ocx_launch_alg_pipe(const ocx_layout* L, const double* zt, const doub
                                int* closed_out, int onepass, hipStream_t st) {
     if (L->G == 0) return hipSuccess;
     return launch_pipe(L, pipe_args(L, zt, yt, eta0, reg, cum, comp, closed_out, onepass), ftl, st);
+}
+
+bool ocx_pipe_persistent_supported(const ocx_layout* L) {
+    return ocx_pipe_supported(L) && L->C == 8 && L->P == 8;
+}
+
+// The persistent instance with `nwaves` waves, whatever the batch's size (the policy above
+// takes it only past one round): ocx_test_alg_pipe_persistent.
+hipError_t ocx_launch_alg_pipe_persistent(const ocx_layout* L, const double* zt, const double* yt,
+                                          int ftl, double eta0, double* reg, double* cum,
+                                          double* comp, int* closed_out, int onepass,
+                                          int64_t nwaves, hipStream_t st) {
+    if (!ocx_pipe_persistent_supported(L) || nwaves <= 0) return hipErrorInvalidValue;
+    if (L->G == 0) return hipSuccess;
+    const PersGeom gm = pers_geometry<8, 8>(ftl);
+    if (gm.err != hipSuccess) return gm.err;
+    return launch_pipe_persistent<8, 8>(pipe_args(L, zt, yt, eta0, reg, cum, comp, closed_out, onepass),
+                                        ftl, nwaves, gm, st);
 }
 
 int64_t ocx_pipe_state_doubles(const ocx_layout* L) {

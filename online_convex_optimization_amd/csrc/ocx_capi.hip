@@ -1602,6 +1602,27 @@ int ocx_test_alg_range(const ocx_layout* L, const double* z_tiled, const double*
     return OCX_OK;
 }
 
+int ocx_test_alg_pipe_persistent(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                                 int ftl, double eta0, int onepass, int64_t nwaves, double* regret,
+                                 double* cum, double* comp, int32_t* closed_out, void* stream) {
+    StreamDevice sd_(stream);
+    if (int rc = check_layout(L)) return rc;
+    if (!ocx_pipe_persistent_supported(L))
+        return fail(OCX_E_UNSUPPORTED, "no persistent instance of the pipelined kernel for this layout");
+    if ((ftl != 0 && ftl != 1) || (onepass != 0 && onepass != 1))
+        return fail(OCX_E_INVALID, "ftl and onepass must be 0 or 1");
+    if (nwaves < 1 || nwaves > ((int64_t)1 << 20)) return fail(OCX_E_INVALID, "nwaves: 1 .. 2^20");
+    if (L->B > 0 && (!regret || (L->z_elems && (!z_tiled || !y_tiled))))
+        return fail(OCX_E_INVALID, "NULL buffer");
+    const hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = ocx_launch_alg_pipe_persistent(L, z_tiled, y_tiled, ftl, eta0, regret, cum,
+                                                        comp, closed_out, onepass, nwaves, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    OCX_HIP(e);
+    OCX_HIP(es);
+    return OCX_OK;
+}
+
 int64_t ocx_test_trailing_batches(void) { return ocx_trailing_batches_run(); }
 
 int ocx_test_gT_regrets_unclean(uint64_t base_seed, int64_t T, int64_t run0, int64_t R,

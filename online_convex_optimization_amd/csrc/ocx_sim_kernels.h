@@ -19,6 +19,13 @@ bool ocx_pipe_supported(const ocx_layout* L);
 hipError_t ocx_launch_alg_pipe(const ocx_layout* L, const double* zt, const double* yt, int ftl,
                                double eta0, double* reg, double* cum, double* comp,
                                int* closed_out, int onepass, hipStream_t st);
+// its persistent instance (a batch of more groups than are resident at once: each wave loops
+// over its share) with `nwaves` waves, whatever the batch's size; the layouts that have one
+bool ocx_pipe_persistent_supported(const ocx_layout* L);
+hipError_t ocx_launch_alg_pipe_persistent(const ocx_layout* L, const double* zt, const double* yt,
+                                          int ftl, double eta0, double* reg, double* cum,
+                                          double* comp, int* closed_out, int onepass,
+                                          int64_t nwaves, hipStream_t st);
 // Regret curves (ocx_alg_curve.hip): FTRL / FTL observed at the K checkpoints ck (device,
 // strictly increasing in [0, T]) in one pass; outputs [B][K] (each nullable).  The curve form
 // of the pipelined kernel where ocx_pipe_supported(L), of the plain kernel otherwise; then

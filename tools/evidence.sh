@@ -65,7 +65,7 @@ for step in "$@"; do
     for C in FETCH_SIZE WRITE_SIZE; do
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --pmc $C --output-format csv -d "${O}_pmc_$C" -o pmc -- python3 "$R/bench.py" --full --steps 2 --warmup 0 --cpu-seconds 0 --two-pass-steps 0 --e2e-steps 1 > "${O}_pmc_$C.log" 2>&1) || fail "pmc $C" $?
     done
-    python tools/pmc_traffic.py --fetch "${O}_pmc_FETCH_SIZE" --write "${O}_pmc_WRITE_SIZE" --kernel "ocx_alg_pipe_kernel<8, 8, 9," --label ocx_alg_pipe_kernel --B 32768 --T 10000 --d 64 --P 8 --passes 1 --out "${O}_traffic.json" > /dev/null || fail traffic $?
+    python tools/pmc_traffic.py --fetch "${O}_pmc_FETCH_SIZE" --write "${O}_pmc_WRITE_SIZE" --kernel "ocx_alg_pipe_kernel<8, 8, 4, false, 2," --label ocx_alg_pipe_kernel --B 32768 --T 10000 --d 64 --P 8 --passes 1 --out "${O}_traffic.json" > /dev/null || fail traffic $?
     head -c 600 "${O}_traffic.json"; echo ;;
   gensq)
     (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT --output-format csv -d "${O}_gensq" -o sq -- python3 "$R/tools/gen_only.py" 32768 10000 64 2 128 > "${O}_gensq.log" 2>&1) || fail gensq $?
