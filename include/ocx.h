@@ -60,7 +60,9 @@
  * nothing existing changed; a caller that needs them looks the symbols up.  The same holds for
  * the step-size sweep symbols (ocx_etas_group, ocx_dev_simulate_alg_etas,
  * ocx_simulate_alg_etas_batch) and the threshold sweep symbols (ocx_smart_thresholds_group,
- * ocx_dev_simulate_smart_thresholds, ocx_simulate_smart_thresholds_batch).
+ * ocx_dev_simulate_smart_thresholds, ocx_simulate_smart_thresholds_batch), and for the SMART
+ * regret-curve symbols (ocx_smart_curve_group, ocx_dev_simulate_smart_curve,
+ * ocx_simulate_smart_curve_batch).
  *
  * Checking the ABI: one intermediate 0.1.x tree exported ocx_ftrl_vs_exact_batch WITH a
  * `norm` argument under the same symbol and the same version number as the release without
@@ -519,6 +521,52 @@ int ocx_simulate_smart_thresholds_batch(const double* z, const double* y, int64_
                                         int64_t d, const double* thresh, int64_t M, double eta0,
                                         double* regret, int64_t* switch_step, int lanes_per_seq,
                                         int device);
+
+/* SMART regret curves: SMART (fast_algorithms.py:118-164) for K pairs (horizon t_k, threshold
+ * thresh[b][k]) in passes over z that each serve a group of consecutive pairs.  The horizons
+ * are NON-DECREASING in [0, T] (equal horizons are legal: SMART and EMP at the same t_k; with
+ * every t_k = T this is the threshold sweep).  SMART's run on the first t rows is the first t
+ * steps of its run on all of them — the FTL leg and the switch test's prefix loss depend on
+ * neither the threshold nor the horizon, FTRL's step size on the global step — so for every k
+ *   regret[b][k], switch_step[b][k]
+ * are bit for bit what ocx_dev_simulate_smart_ex's lane-group kernel gives on
+ * (z[b][:t_k], y[b][:t_k]) with thresh[b] = thresh[b][k], the same layout (it does not depend
+ * on T) and the same flags.  switch_step lies in [0, t_k) or is -1; t_k = 0 gives 0.0 and -1.
+ * A column freezes at its horizon: its loss as it stands, and as comparator FTL(theta_ftl
+ * after t_k steps) over rows 0 .. t_k-1, streamed there in the reference's order or, with
+ * OCX_ALG_CLOSED_COMPARATOR, t_k/2 - ||theta_ftl|| where the first t_k steps certify it.  The
+ * certificate is per (sequence, column); a column's bits depend neither on the group size nor
+ * on its neighbours.  A pass loops to its group's last horizon only, and a step re-scans only
+ * while some column of the group is both unswitched and before its horizon.  NaN and ±inf
+ * thresholds as in the threshold sweep; OCX_SMART_CLOSED_PREFIX and its guard band are
+ * unchanged (they depend on t and d, never on T).
+ *
+ * pairs one pass over z serves in layout L (1: one pass per pair; negative ocx_status on
+ * error).  Above 1 only where that group measured faster than K single-threshold calls on
+ * truncated batches; never above the smallest group that holds K. */
+int ocx_smart_curve_group(const ocx_layout* L, int64_t K);
+
+/* device: horizons is a HOST array [K], read and validated (order, range) at call time: a bad
+ * list returns OCX_E_INVALID and nothing is launched.  thresh is a DEVICE array [B][K]
+ * row-major; regret [B][K] device, switch_step [B][K] int64 device, nullable.  flags: those of
+ * ocx_dev_simulate_smart_ex; unknown flags are rejected.  stats (nullable, device uint64 [2]),
+ * per launch (ceil(K / group) launches): += (sequence, step) pairs that re-scanned,
+ * += (sequence, column) pairs that took the closed comparator.  K == 0, B == 0 and T == 0 are
+ * valid; asynchronous, no allocation, no sync: capture-safe like the other dev entry points
+ * (a captured graph keeps the horizons it was captured with). */
+int ocx_dev_simulate_smart_curve(const ocx_layout* L, const double* z_tiled,
+                                 const double* y_tiled, const int64_t* horizons,
+                                 const double* thresh, int64_t K, double eta0, double* regret,
+                                 int64_t* switch_step, int flags, unsigned long long* stats,
+                                 void* stream);
+
+/* host: numpy buffers in, [B][K] out; horizons HOST [K], thresh HOST [B][K]; switch_step
+ * nullable.  Bit-exact layouts (lanes_per_seq 1 / -k): flags 0; other modes: both closed
+ * forms, as ocx_simulate_smart_thresholds_batch. */
+int ocx_simulate_smart_curve_batch(const double* z, const double* y, int64_t B, int64_t T,
+                                   int64_t d, const int64_t* horizons, const double* thresh,
+                                   int64_t K, double eta0, double* regret, int64_t* switch_step,
+                                   int lanes_per_seq, int device);
 
 /* exact_ftl.py:306-333 on device; a_tiled is the actions [B][T+1][d] tiled with a
  * layout of T+1 steps (z/y use L, actions use La with La->T == L->T + 1). */

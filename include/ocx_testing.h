@@ -80,6 +80,16 @@ int ocx_test_simulate_smart_thresholds(const ocx_layout* L, const double* z_tile
                                        int flags, unsigned long long* stats, int group,
                                        void* stream);
 
+/* ocx_dev_simulate_smart_curve with the group size forced to `group` (1, 2 or 4) instead of
+ * ocx_smart_curve_group's choice.  OCX_E_UNSUPPORTED where that form is not instantiated for
+ * the layout (group 2 above 16 coordinates per lane, group 4 above 8).  Asynchronous like the
+ * product call. */
+int ocx_test_simulate_smart_curve(const ocx_layout* L, const double* z_tiled,
+                                  const double* y_tiled, const int64_t* horizons,
+                                  const double* thresh, int64_t K, double eta0, double* regret,
+                                  int64_t* switch_step, int flags, unsigned long long* stats,
+                                  int group, void* stream);
+
 /* Batches that have entered the trailing pipeline (ocx_run_gen_sim_trailing) in this process
  * so far: lets a test assert that a call took that path rather than the sequential loop. */
 int64_t ocx_test_trailing_batches(void);

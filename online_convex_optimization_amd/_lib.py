@@ -107,6 +107,11 @@ SIGNATURES = {
                                                   c_double, c_vp, c_vp, c_int, c_vp, c_vp]),
     "ocx_simulate_smart_thresholds_batch": (c_int, [c_dp, c_dp, c_i64, c_i64, c_i64, c_dp, c_i64,
                                                     c_double, c_dp, c_i64p, c_int, c_int]),
+    "ocx_smart_curve_group": (c_int, [ctypes.POINTER(Layout), c_i64]),
+    "ocx_dev_simulate_smart_curve": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_i64p, c_vp,
+                                             c_i64, c_double, c_vp, c_vp, c_int, c_vp, c_vp]),
+    "ocx_simulate_smart_curve_batch": (c_int, [c_dp, c_dp, c_i64, c_i64, c_i64, c_i64p, c_dp,
+                                               c_i64, c_double, c_dp, c_i64p, c_int, c_int]),
     "ocx_dev_ftrl_vs_exact_ex": (c_int,[ctypes.POINTER(Layout), c_vp, c_vp, c_double, c_vp, c_vp,
                                          c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
     "ocx_gT_sweep": (c_int, [c_i64p, c_int, c_i64, c_u64, c_i64, c_double, c_int, c_dp, c_dp]),
@@ -141,6 +146,9 @@ TEST_SIGNATURES = {
     "ocx_test_simulate_smart_thresholds": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_vp, c_i64,
                                                    c_double, c_vp, c_vp, c_int, c_vp, c_int,
                                                    c_vp]),
+    "ocx_test_simulate_smart_curve": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_i64p, c_vp,
+                                              c_i64, c_double, c_vp, c_vp, c_int, c_vp, c_int,
+                                              c_vp]),
     "ocx_test_trailing_batches": (c_i64, []),
 }
 OCX_VERSION = 400  # include/ocx.h OCX_VERSION: the ABI these signatures describe

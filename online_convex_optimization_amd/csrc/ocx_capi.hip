@@ -639,6 +639,81 @@ int ocx_test_simulate_smart_thresholds(const ocx_layout* L, const double* z_tile
                                          switch_step, flags, stats, group, stream);
 }
 
+// the smallest instantiated group that holds K pairs, capped at `best`
+static int smart_curve_group_for(const ocx_layout* L, int64_t K, int best) {
+    int g = best;
+    while (g > 1 && (g / 2 >= K || !ocx_smart_curve_instance(L, g))) g /= 2;
+    return g;
+}
+
+int ocx_smart_curve_group(const ocx_layout* L, int64_t K) {
+    if (int rc = check_layout(L)) return rc;
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    return smart_curve_group_for(L, K, ocx_smart_curve_best_group(L));
+}
+
+// the horizons of a SMART curve (host): non-decreasing, inside [0, T]
+static int check_horizons(const int64_t* horizons, int64_t K, int64_t T) {
+    if (K > 0 && !horizons) return fail(OCX_E_INVALID, "NULL horizons");
+    for (int64_t k = 0; k < K; ++k) {
+        if (horizons[k] < 0 || horizons[k] > T)
+            return fail(OCX_E_INVALID, "horizon " + std::to_string(horizons[k]) +
+                                           " outside [0, T = " + std::to_string(T) + "]");
+        if (k > 0 && horizons[k] < horizons[k - 1])
+            return fail(OCX_E_INVALID, "horizons must be non-decreasing");
+    }
+    return OCX_OK;
+}
+
+// group 0: the dispatcher's choice
+static int dev_simulate_smart_curve(const ocx_layout* L, const double* z_tiled,
+                                    const double* y_tiled, const int64_t* horizons,
+                                    const double* thresh, int64_t K, double eta0, double* regret,
+                                    int64_t* switch_step, int flags, unsigned long long* stats,
+                                    int group, void* stream) {
+    StreamDevice sd_(stream);
+    if (int rc = check_layout(L)) return rc;
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    if (flags & ~(OCX_SMART_CLOSED_PREFIX | OCX_ALG_CLOSED_COMPARATOR | OCX_ALG_CLIPPED_ROWS))
+        return fail(OCX_E_INVALID, "unknown flags");
+    if (group != 0 && group != 1 && group != 2 && group != 4)
+        return fail(OCX_E_INVALID, "group must be 1, 2 or 4");
+    if (group != 0 && !ocx_smart_curve_instance(L, group))
+        return fail(OCX_E_UNSUPPORTED, "no group-" + std::to_string(group) + " form at " +
+                                           std::to_string(L->C) + " coordinates per lane");
+    if (int rc = check_horizons(horizons, K, L->T)) return rc;
+    if (K == 0 || L->G == 0) return OCX_OK;
+    if (!thresh || !regret) return fail(OCX_E_INVALID, "NULL thresh/regret");
+    if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL input buffer");
+    if (group == 0) group = smart_curve_group_for(L, K, ocx_smart_curve_best_group(L));
+    OCX_HIP(ocx_launch_smart_curve(
+        L, z_tiled, y_tiled, horizons, thresh, K, eta0, regret, switch_step,
+        (flags & OCX_SMART_CLOSED_PREFIX) ? 1 : 0,
+        (flags & (OCX_ALG_CLOSED_COMPARATOR | OCX_ALG_CLIPPED_ROWS)) ? 1 : 0, stats, group,
+        (hipStream_t)stream));
+    return OCX_OK;
+}
+
+int ocx_dev_simulate_smart_curve(const ocx_layout* L, const double* z_tiled,
+                                 const double* y_tiled, const int64_t* horizons,
+                                 const double* thresh, int64_t K, double eta0, double* regret,
+                                 int64_t* switch_step, int flags, unsigned long long* stats,
+                                 void* stream) {
+    return dev_simulate_smart_curve(L, z_tiled, y_tiled, horizons, thresh, K, eta0, regret,
+                                    switch_step, flags, stats, 0, stream);
+}
+
+int ocx_test_simulate_smart_curve(const ocx_layout* L, const double* z_tiled,
+                                  const double* y_tiled, const int64_t* horizons,
+                                  const double* thresh, int64_t K, double eta0, double* regret,
+                                  int64_t* switch_step, int flags, unsigned long long* stats,
+                                  int group, void* stream) {
+    if (group != 1 && group != 2 && group != 4)
+        return fail(OCX_E_INVALID, "group must be 1, 2 or 4");
+    return dev_simulate_smart_curve(L, z_tiled, y_tiled, horizons, thresh, K, eta0, regret,
+                                    switch_step, flags, stats, group, stream);
+}
+
 int ocx_dev_replay(const ocx_layout* L, const ocx_layout* La, const double* z_tiled,
                    const double* y_tiled, const double* a_tiled, double* cum_loss,
                    double* comp_loss, void* stream) {
@@ -935,6 +1010,51 @@ int ocx_simulate_smart_thresholds_batch(const double* z, const double* y, int64_
                                                    cx->thr.as<double>(), M, eta0,
                                                    cx->out.as<double>(), cx->sw.as<int64_t>(),
                                                    flags, nullptr, st))
+        return rc;
+    OCX_HIP(hipMemcpyAsync(regret, cx->out.p, nm * 8, hipMemcpyDeviceToHost, st));
+    if (switch_step)
+        OCX_HIP(hipMemcpyAsync(switch_step, cx->sw.p, nm * 8, hipMemcpyDeviceToHost, st));
+    OCX_HIP(hipStreamSynchronize(st));
+    return OCX_OK;
+}
+
+int ocx_simulate_smart_curve_batch(const double* z, const double* y, int64_t B, int64_t T,
+                                   int64_t d, const int64_t* horizons, const double* thresh,
+                                   int64_t K, double eta0, double* regret, int64_t* switch_step,
+                                   int lanes_per_seq, int device) {
+    ocx_layout L;
+    if (int rc = ocx_layout_init(B, T, d, lanes_per_seq, &L)) return rc;
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    if (int rc = check_horizons(horizons, K, T)) return rc;  // before anything is queued
+    if (B == 0 || K == 0) return OCX_OK;
+    if ((T * d > 0 && !z) || (T > 0 && !y) || !thresh || !regret)
+        return fail(OCX_E_INVALID, "NULL argument");
+    DevCtx* cx;
+    if (int rc = ctx_enter(device, &cx)) return rc;
+    std::lock_guard<std::mutex> lk(cx->mu);
+    hipStream_t st = cx->stream;
+    const size_t nz = (size_t)(B * T * d), ny = (size_t)(B * T), nm = (size_t)(B * K);
+    OCX_HIP(cx->zraw.ensure(nz * 8));
+    OCX_HIP(cx->yraw.ensure(ny * 8));
+    OCX_HIP(cx->zt.ensure((size_t)L.z_elems * 8));
+    OCX_HIP(cx->yt.ensure((size_t)L.y_elems * 8));
+    OCX_HIP(cx->thr.ensure(nm * 8));
+    OCX_HIP(cx->out.ensure(nm * 8));
+    OCX_HIP(cx->sw.ensure(nm * 8));
+    if (nz) OCX_HIP(hipMemcpyAsync(cx->zraw.p, z, nz * 8, hipMemcpyHostToDevice, st));
+    if (ny) OCX_HIP(hipMemcpyAsync(cx->yraw.p, y, ny * 8, hipMemcpyHostToDevice, st));
+    OCX_HIP(hipMemcpyAsync(cx->thr.p, thresh, nm * 8, hipMemcpyHostToDevice, st));
+    OCX_HIP(ocx_launch_pack(&L, cx->zraw.as<double>(), cx->yraw.as<double>(), cx->zt.as<double>(),
+                            cx->yt.as<double>(), st));
+    // bit-exact modes: the reference's prefix re-scan and streamed comparator; the others:
+    // guarded closed-form prefix, certified closed-form comparator
+    const int flags = (lanes_per_seq == 1 || lanes_per_seq < 0)
+                          ? 0
+                          : (OCX_SMART_CLOSED_PREFIX | OCX_ALG_CLOSED_COMPARATOR);
+    if (int rc = ocx_dev_simulate_smart_curve(&L, cx->zt.as<double>(), cx->yt.as<double>(),
+                                              horizons, cx->thr.as<double>(), K, eta0,
+                                              cx->out.as<double>(), cx->sw.as<int64_t>(), flags,
+                                              nullptr, st))
         return rc;
     OCX_HIP(hipMemcpyAsync(regret, cx->out.p, nm * 8, hipMemcpyDeviceToHost, st));
     if (switch_step)

@@ -144,6 +144,19 @@ hipError_t ocx_launch_smart_thresholds(const ocx_layout* L, const double* zt, co
                                        const double* th, int64_t M, double eta0, double* reg,
                                        int64_t* sw, int closed_prefix, int closed_comp,
                                        unsigned long long* stats, int group, hipStream_t st);
+// SMART regret curves (ocx_smart_curve.hip): the K pairs (horizon hz[k], HOST, read at call
+// time, non-decreasing in [0, T]; threshold th[b][k], device) in passes of at most `group`
+// (1, 2 or 4; ocx_smart_curve_instance) consecutive pairs, each looping to its last horizon;
+// column k the bits of ocx_launch_smart_closed on the rows truncated at hz[k]; reg / sw
+// [B][K] (sw nullable); stats per launch: += re-scanned (sequence, step) pairs, += (sequence,
+// column) pairs with the closed comparator.  ocx_smart_curve_best_group: the group the
+// measurements chose.
+bool ocx_smart_curve_instance(const ocx_layout* L, int group);
+int ocx_smart_curve_best_group(const ocx_layout* L);
+hipError_t ocx_launch_smart_curve(const ocx_layout* L, const double* zt, const double* yt,
+                                  const int64_t* hz, const double* th, int64_t K, double eta0,
+                                  double* reg, int64_t* sw, int closed_prefix, int closed_comp,
+                                  unsigned long long* stats, int group, hipStream_t st);
 // SMART with one wavefront per sequence (ocx_smart_wave.hip), d <= 64
 hipError_t ocx_launch_smart_wave(const ocx_layout* L, const double* zt, const double* yt,
                                  const double* th, double eta0, double* reg, int64_t* sw,

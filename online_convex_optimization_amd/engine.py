@@ -225,6 +225,68 @@ def simulate_smart_thresholds_batch(z, y, thresholds, eta0: float = SQRT2, *,
     return (reg, sw) if return_switch else reg
 
 
+def _horizons(horizons, T: int) -> np.ndarray:
+    """The horizons of a SMART regret curve as a contiguous int64 array: a one-dimensional
+    list of integers, non-decreasing (equal horizons are legal: SMART and EMP at the same
+    t_k), inside [0, T].  Booleans and non-integral floats are rejected.  Raises ValueError
+    otherwise."""
+    try:
+        a = np.asarray(horizons)
+    except Exception as e:  # ragged lists
+        raise ValueError(f"horizons must be a one-dimensional list of integers: {e}") from None
+    if a.ndim != 1:
+        raise ValueError(f"horizons must be one-dimensional, got shape {a.shape}")
+    if a.size and not (np.issubdtype(a.dtype, np.integer) or
+                       (np.issubdtype(a.dtype, np.floating) and np.all(np.isfinite(a)) and
+                        np.all(a == np.floor(a)))):
+        raise ValueError(f"horizons must be integers, got dtype {a.dtype}")
+    hz = np.ascontiguousarray(a, dtype=np.int64)
+    if hz.size and (hz.min() < 0 or hz.max() > int(T)):
+        raise ValueError(f"horizons must lie in [0, T = {int(T)}], got {hz.min()}..{hz.max()}")
+    if np.any(np.diff(hz) < 0):
+        raise ValueError("horizons must be non-decreasing")
+    return hz
+
+
+def _smart_curve_thresholds(thresholds, hz: np.ndarray, B: int) -> np.ndarray:
+    """[B, K] thresholds of a SMART curve: ``thresholds`` through _thresholds, or SMART's own
+    sqrt(2 t_k) when None; one column per horizon."""
+    if thresholds is None:
+        thresholds = np.sqrt(2.0 * hz.astype(np.float64))
+    th = _thresholds(thresholds, B)
+    if th.shape[1] != hz.size:
+        raise ValueError(f"need one threshold column per horizon: {hz.size} horizons, "
+                         f"{th.shape[1]} threshold columns")
+    return th
+
+
+def simulate_smart_curve_batch(z, y, horizons, thresholds=None, eta0: float = SQRT2, *,
+                               lanes_per_seq: int = LANES_BEST, device: int = 0,
+                               return_switch: bool = False):
+    """SMART regret curves: SMART (fast_algorithms.py:118-164) over B sequences for K pairs
+    (horizon t_k, threshold), each pass over z serving a group of consecutive pairs and
+    stopping at the group's last horizon (ocx_simulate_smart_curve_batch).
+
+    ``horizons`` [K]: integers, non-decreasing in [0, T]; ``thresholds`` [K] or [B, K]
+    (None: SMART's own sqrt(2 t_k)).  Column k is simulate_smart_batch's lane-group kernel on
+    (z[:, :t_k], y[:, :t_k]) with thresh = thresholds[..., k]: bit for bit in the bit-exact
+    modes (lanes_per_seq 1 / -k: the reference's prefix re-scan and streamed comparator), both
+    closed forms in the others.  Returns regret [B, K] or, with ``return_switch``, (regret,
+    switch_step [B, K] int64, in [0, t_k) or -1 = never)."""
+    z = _f64(z)
+    y = _f64(y)
+    B, T, d = _check_zy(z, y)
+    hz = _horizons(horizons, T)
+    th = _smart_curve_thresholds(thresholds, hz, B)
+    K = int(hz.size)
+    reg = np.zeros((B, K))
+    sw = np.full((B, K), -1, dtype=np.int64)
+    _lib.call("ocx_simulate_smart_curve_batch", ptr(z), ptr(y), B, T, d,
+              hz.ctypes.data_as(_lib.c_i64p), ptr(th), K, float(eta0), ptr(reg),
+              sw.ctypes.data_as(_lib.c_i64p), int(lanes_per_seq), int(device))
+    return (reg, sw) if return_switch else reg
+
+
 def replay_batch(z, y, actions, *, device: int = 0):
     """exact_ftl.py:306-333 over B sequences: actions [B, T+1, d] → (cum_loss, comp_loss)."""
     z = _f64(z)
@@ -805,6 +867,78 @@ class DeviceBatch:
         else:
             self._call("ocx_test_simulate_smart_thresholds", *args, int(_group), self._sp)
         self._keep_th = self._hold(th)
+        return out
+
+    def simulate_smart_curve(self, horizons, thresholds=None, eta0: float = SQRT2, *,
+                             closed_prefix: Optional[bool] = None,
+                             closed_comparator: Optional[bool] = None, stats=None,
+                             _group=None):
+        """SMART regret curves of the resident batch (ocx_dev_simulate_smart_curve, async):
+        SMART for K pairs (horizon t_k, threshold), each pass over z serving
+        ocx_smart_curve_group(L, K) consecutive pairs and stopping at their last horizon.
+        ``horizons`` [K]: integers, non-decreasing in [0, T] (validated here; equal horizons
+        are legal); ``thresholds`` [K] or [B, K] (validated through _thresholds; None: SMART's
+        own sqrt(2 t_k)).  Returns device tensors ``regret`` [B, K] float64 and ``switch_step``
+        [B, K] int64 (in [0, t_k), or -1 = never); column k is what
+        simulate_smart(thresholds[..., k], eta0, stats=...) gives on a batch of the first t_k
+        rows, bit for bit in the same layout.  ``closed_prefix`` / ``closed_comparator``
+        default as in simulate_smart; the closed comparator is certified per (sequence,
+        column) by that column's first t_k steps.  ``stats`` ([2] int64 device tensor,
+        optional) accumulates, per pass, the (sequence, step) pairs that re-scanned and the
+        (sequence, column) pairs that took the closed comparator.  (``_group``: tests and
+        tools/smart_curve_probe.py force the group size through include/ocx_testing.h.)"""
+        torch = self.torch
+        B = int(self.L.B)
+        hz = _horizons(horizons, self.L.T)
+        tha = _smart_curve_thresholds(thresholds, hz, B)
+        K = int(hz.size)
+        if closed_prefix is None:
+            closed_prefix = not self.exact
+        if closed_comparator is None:
+            closed_comparator = not self.exact
+        flags = ((_lib.OCX_SMART_CLOSED_PREFIX if closed_prefix else 0) |
+                 (_lib.OCX_ALG_CLOSED_COMPARATOR if closed_comparator else 0))
+        with torch.cuda.device(self.device), self._on_stream():
+            th = torch.as_tensor(tha).to(self.device)
+            out = {"regret": torch.zeros((B, K), dtype=torch.float64, device=self.device),
+                   "switch_step": torch.full((B, K), -1, dtype=torch.int64, device=self.device)}
+        args = (self._lp(), self.z.data_ptr(), self.y.data_ptr(),
+                hz.ctypes.data_as(_lib.c_i64p), th.data_ptr() if B * K else None, K, float(eta0),
+                out["regret"].data_ptr() if B * K else None,
+                out["switch_step"].data_ptr() if B * K else None, flags,
+                stats.data_ptr() if stats is not None else None)
+        if _group is None:
+            self._call("ocx_dev_simulate_smart_curve", *args, self._sp)
+        else:
+            self._call("ocx_test_simulate_smart_curve", *args, int(_group), self._sp)
+        self._keep_th = self._hold(th)
+        return out
+
+    def comparison_curves(self, checkpoints, g_emp=None, eta0: float = SQRT2):
+        """The four lines of the reference's comparison figure (fast_driver.py:71-127) against
+        the horizon, from this resident batch: a dict of [B, K] device tensors ``FTRL``,
+        ``FTL``, ``SMART`` (threshold sqrt(2 t_k)) and, when ``g_emp`` ([K], the empirical
+        g(t_k)) is given, ``EMP``.  ``checkpoints`` is strictly increasing in [0, T].  FTRL
+        comes from simulate_alg_curve; the others from ONE simulate_smart_curve call over the
+        2K or 3K pairs sorted by horizon, with thresholds +inf (a column that never switches
+        is FTL's regret), sqrt(2 t_k) and g_emp[k].  Column k of each is the regret on the
+        batch truncated at t_k."""
+        ck = _checkpoints(checkpoints, self.L.T)
+        K = int(ck.size)
+        cols = [("FTL", np.full(K, np.inf)), ("SMART", np.sqrt(2.0 * ck.astype(np.float64)))]
+        if g_emp is not None:
+            g = _etas(g_emp)
+            if g.shape != (K,):
+                raise ValueError(f"g_emp must be [K = {K}], got shape {g.shape}")
+            cols.append(("EMP", g))
+        n = len(cols)
+        hz = np.repeat(ck, n)                                    # t_0 × n, t_1 × n, ...
+        th = np.stack([c[1] for c in cols], axis=1).reshape(-1)  # interleaved the same way
+        out = {"FTRL": self.simulate_alg_curve(ck, 0, eta0)["regret"]}
+        reg = self.simulate_smart_curve(hz, th, eta0)["regret"]
+        with self._on_stream():
+            for i, (name, _) in enumerate(cols):
+                out[name] = reg[:, i::n].contiguous()
         return out
 
     def simulate_twin32(self, algo: int = 0, eta0: float = SQRT2, thresh=None):
