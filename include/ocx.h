@@ -508,7 +508,12 @@ int ocx_smart_thresholds_group(const ocx_layout* L, int64_t M);
  * them.  stats (nullable, device uint64 [2]), per launch (ceil(M / group) launches):
  * += (sequence, step) pairs that re-scanned, += sequences that took the closed comparator.
  * M == 0, B == 0 and T == 0 are valid (T == 0 gives zeros and -1);
- * asynchronous, no allocation, no sync: capture-safe like the other dev entry points. */
+ * asynchronous, no allocation, no sync: capture-safe like the other dev entry points.
+ * With flags 0 and stats NULL in an exact layout (chain, or one lane per sequence) at d <= 64
+ * and B <= 32768, this call and ocx_dev_simulate_smart_curve run the one-wave-per-sequence
+ * kernel (up to eight columns per prefix re-scan) where it measured faster:
+ * the same bits.  OCX_SMART_KERNEL=lanes in the environment holds them on the lane-group
+ * kernel, as it does ocx_dev_simulate_smart. */
 int ocx_dev_simulate_smart_thresholds(const ocx_layout* L, const double* z_tiled,
                                       const double* y_tiled, const double* thresh, int64_t M,
                                       double eta0, double* regret, int64_t* switch_step,

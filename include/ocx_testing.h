@@ -90,6 +90,23 @@ int ocx_test_simulate_smart_curve(const ocx_layout* L, const double* z_tiled,
                                   int64_t* switch_step, int flags, unsigned long long* stats,
                                   int group, void* stream);
 
+/* The one-wave-per-sequence form of the two SMART sweeps (ocx_smart_wave_cols_kernel), forced:
+ * always that kernel, in any layout and at any batch size, in launches of `group` (1, 2, 4 or
+ * 8) consecutive columns, instead of the dispatch of ocx_dev_simulate_smart_thresholds /
+ * ocx_dev_simulate_smart_curve.  Re-scan mode only (no flags).  Column m is the pair
+ * (horizons[m], thresh[b][m]); horizons is a HOST array of M non-decreasing values in [0, T],
+ * read at call time, or NULL for the threshold sweep (every horizon T).  thresh, regret and
+ * switch_step (nullable) are [B][M] device arrays.  The kernel adds in the reference's order
+ * whatever the layout, so a butterfly layout gets the exact modes' bits here.  stats (device
+ * [2], nullable): stats[0] += the (sequence, step) pairs whose switch test ran, once per step
+ * however many columns of the launch needed it; stats[1] is left alone.  OCX_E_UNSUPPORTED
+ * for d > 64.  Asynchronous like the product calls. */
+int ocx_test_simulate_smart_wave_cols(const ocx_layout* L, const double* z_tiled,
+                                      const double* y_tiled, const int64_t* horizons,
+                                      const double* thresh, int64_t M, double eta0,
+                                      double* regret, int64_t* switch_step,
+                                      unsigned long long* stats, int group, void* stream);
+
 /* Batches that have entered the trailing pipeline (ocx_run_gen_sim_trailing) in this process
  * so far: lets a test assert that a call took that path rather than the sequential loop. */
 int64_t ocx_test_trailing_batches(void);

@@ -149,6 +149,9 @@ TEST_SIGNATURES = {
     "ocx_test_simulate_smart_curve": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_i64p, c_vp,
                                               c_i64, c_double, c_vp, c_vp, c_int, c_vp, c_int,
                                               c_vp]),
+    "ocx_test_simulate_smart_wave_cols": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_i64p, c_vp,
+                                                  c_i64, c_double, c_vp, c_vp, c_vp, c_int,
+                                                  c_vp]),
     "ocx_test_trailing_batches": (c_i64, []),
 }
 OCX_VERSION = 400  # include/ocx.h OCX_VERSION: the ABI these signatures describe

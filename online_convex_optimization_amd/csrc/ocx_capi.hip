@@ -592,6 +592,22 @@ int ocx_smart_thresholds_group(const ocx_layout* L, int64_t M) {
     return thresholds_group_for(L, M, ocx_thresholds_best_group(L));
 }
 
+// The sweeps' one-wave-per-sequence form (ocx_smart_wave_cols.hip) is taken, with the group
+// unforced, in the re-scan mode without a stats tensor, in the exact layouts (in a butterfly
+// layout its reference-order sums are not the lane-group instance's bits) and at the single
+// call's own sizes (ocx_launch_smart), where the measurements found it faster than both the
+// lane-group sweep and M single calls (ocx_smart_wave_cols_worth).  OCX_SMART_KERNEL=lanes
+// holds the sweeps on the lane-group kernel, as it does the single call; =wave takes the wave
+// form wherever the rest of the rule allows it, measured faster or not.
+static bool smart_sweep_takes_wave(const ocx_layout* L, int64_t M, int flags, const void* stats,
+                                   int group) {
+    if (group != 0 || flags != 0 || stats) return false;
+    if (!(L->chain || L->P == 1)) return false;
+    if (L->d > 64 || L->B > 32768) return false;
+    if (const char* e = std::getenv("OCX_SMART_KERNEL")) return std::strcmp(e, "wave") == 0;
+    return ocx_smart_wave_cols_worth(L, M);
+}
+
 // group 0: the dispatcher's choice
 static int dev_simulate_smart_thresholds(const ocx_layout* L, const double* z_tiled,
                                          const double* y_tiled, const double* thresh, int64_t M,
@@ -611,6 +627,12 @@ static int dev_simulate_smart_thresholds(const ocx_layout* L, const double* z_ti
     if (M == 0 || L->G == 0) return OCX_OK;
     if (!thresh || !regret) return fail(OCX_E_INVALID, "NULL thresh/regret");
     if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL input buffer");
+    if (smart_sweep_takes_wave(L, M, flags, stats, group)) {
+        OCX_HIP(ocx_launch_smart_wave_cols(L, z_tiled, y_tiled, nullptr, thresh, M, eta0, regret,
+                                           switch_step, nullptr, ocx_smart_wave_cols_group(L, M),
+                                           (hipStream_t)stream));
+        return OCX_OK;
+    }
     if (group == 0) group = thresholds_group_for(L, M, ocx_thresholds_best_group(L));
     OCX_HIP(ocx_launch_smart_thresholds(
         L, z_tiled, y_tiled, thresh, M, eta0, regret, switch_step,
@@ -685,6 +707,12 @@ static int dev_simulate_smart_curve(const ocx_layout* L, const double* z_tiled,
     if (K == 0 || L->G == 0) return OCX_OK;
     if (!thresh || !regret) return fail(OCX_E_INVALID, "NULL thresh/regret");
     if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL input buffer");
+    if (smart_sweep_takes_wave(L, K, flags, stats, group)) {
+        OCX_HIP(ocx_launch_smart_wave_cols(L, z_tiled, y_tiled, horizons, thresh, K, eta0, regret,
+                                           switch_step, nullptr, ocx_smart_wave_cols_group(L, K),
+                                           (hipStream_t)stream));
+        return OCX_OK;
+    }
     if (group == 0) group = smart_curve_group_for(L, K, ocx_smart_curve_best_group(L));
     OCX_HIP(ocx_launch_smart_curve(
         L, z_tiled, y_tiled, horizons, thresh, K, eta0, regret, switch_step,
@@ -712,6 +740,29 @@ int ocx_test_simulate_smart_curve(const ocx_layout* L, const double* z_tiled,
         return fail(OCX_E_INVALID, "group must be 1, 2 or 4");
     return dev_simulate_smart_curve(L, z_tiled, y_tiled, horizons, thresh, K, eta0, regret,
                                     switch_step, flags, stats, group, stream);
+}
+
+int ocx_test_simulate_smart_wave_cols(const ocx_layout* L, const double* z_tiled,
+                                      const double* y_tiled, const int64_t* horizons,
+                                      const double* thresh, int64_t M, double eta0,
+                                      double* regret, int64_t* switch_step,
+                                      unsigned long long* stats, int group, void* stream) {
+    StreamDevice sd_(stream);
+    if (int rc = check_layout(L)) return rc;
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    if (!ocx_smart_wave_cols_instance(group))
+        return fail(OCX_E_INVALID, "group must be 1, 2, 4 or 8");
+    if (L->d > 64)
+        return fail(OCX_E_UNSUPPORTED, "the one-wave-per-sequence form holds d <= 64, got d = " +
+                                           std::to_string(L->d));
+    if (horizons)
+        if (int rc = check_horizons(horizons, M, L->T)) return rc;
+    if (M == 0 || L->B == 0) return OCX_OK;
+    if (!thresh || !regret) return fail(OCX_E_INVALID, "NULL thresh/regret");
+    if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL input buffer");
+    OCX_HIP(ocx_launch_smart_wave_cols(L, z_tiled, y_tiled, horizons, thresh, M, eta0, regret,
+                                       switch_step, stats, group, (hipStream_t)stream));
+    return OCX_OK;
 }
 
 int ocx_dev_replay(const ocx_layout* L, const ocx_layout* La, const double* z_tiled,

@@ -161,6 +161,23 @@ hipError_t ocx_launch_smart_curve(const ocx_layout* L, const double* zt, const d
 hipError_t ocx_launch_smart_wave(const ocx_layout* L, const double* zt, const double* yt,
                                  const double* th, double eta0, double* reg, int64_t* sw,
                                  hipStream_t st);
+// its NT-column form (ocx_smart_wave_cols.hip), re-scan mode only, d <= 64 (else
+// hipErrorNotSupported): the M pairs (horizon hz[m], HOST, read at call time, non-decreasing in
+// [0, T]; NULL: every horizon T, the threshold sweep; threshold th[b][m], device) in launches
+// of at most `group` (1, 2, 4 or 8) consecutive columns, one prefix re-scan per step for all of
+// a launch's columns; column m the bits of ocx_launch_smart_wave on the rows truncated at
+// hz[m] — the reference's summation order in any layout; reg / sw [B][M] (sw nullable);
+// stats[0] (nullable) += (sequence, step) pairs whose switch test ran, per launch.  Allocates
+// nothing and never synchronises.  ocx_smart_wave_cols_group: the group the measurements chose;
+// ocx_smart_wave_cols_worth: whether they found this form faster than the lane-group sweep and
+// than M single calls for M columns of this layout (the sweeps' dispatch asks).
+bool ocx_smart_wave_cols_instance(int group);
+int ocx_smart_wave_cols_group(const ocx_layout* L, int64_t M);
+bool ocx_smart_wave_cols_worth(const ocx_layout* L, int64_t M);
+hipError_t ocx_launch_smart_wave_cols(const ocx_layout* L, const double* zt, const double* yt,
+                                      const int64_t* hz, const double* th, int64_t M, double eta0,
+                                      double* reg, int64_t* sw, unsigned long long* stats,
+                                      int group, hipStream_t st);
 hipError_t ocx_launch_replay(const ocx_layout* L, const double* zt, const double* yt,
                              const double* at, double* cum, double* comp, hipStream_t st);
 // exact FTL prefix actions [B][T+1][d] (closed form, l2 ball; ocx_sim.hip)

@@ -1,0 +1,481 @@
+// ocx_smart_wave_cols.hip — the NT-column form of ocx_smart_wave_kernel (ocx_smart_wave.hip):
+// SMART with one wavefront per sequence for up to NT (horizon, threshold) pairs per prefix
+// re-scan.
+//
+// The prefix loss s_loss of step t (fast_algorithms.py:157-160) depends on neither the
+// threshold nor the horizon, so in the re-scan mode one O(t·d) scan decides the switch test of
+// every column.  What a column owns in the wave form is small: theta_ftrl (coordinate `lane`),
+// its total loss, its switch step and a flag.  theta_ftl, ftl_loss, the FTL leg of every step
+// (kSpec steps ahead), one prefix_loss_multi per speculated group and one comparator scan per
+// distinct horizon exist once per sequence.
+//
+// The summation pieces — ordered_sum, prefix_loss, prefix_loss_multi with its DMAX = 8 and
+// DMAX = 0 row paths, the tile addressing by readlane — are ocx_smart_wave_kernel's, operation
+// for operation, written out a second time (that kernel stays as it is).  They add in the
+// reference's order whatever the layout, so every column carries the C oracle's bits.
+//
+// Columns.  Column m of a launch is (h[m], th[b][k0 + m]); the horizons are non-decreasing, so
+// the frozen columns are always a prefix [0, mf) of the launch and the next horizon is h[mf].
+// A speculated group never crosses it: K = min(kSpec, h[mf] − t).  When t reaches h[mf] every
+// column with that horizon freezes: loss = its own total if it has switched, else ftl_loss;
+// comparator = prefix_loss(FTL(theta_ftl), h), once for all of them.  The threshold sweep is
+// the case h[m] = T.  The spare columns of a tail launch (m >= nt) are never live: they are
+// neither tested nor written and do not keep the re-scan alive.
+//
+// Before its switch a column has no total of its own: at the switch step it takes fl[ks], the
+// same additions from 0 as the single kernel's `total_loss += lf[k]`.  A column that switches
+// at step ks of a group replays the group's later steps as FTRL steps; a column switched
+// before the group takes FTRL steps for all of them.  The FTRL steps of the NT columns run side
+// by side, their ordered sums interleaved through NT x 64 LDS slots as prefix_loss_multi's
+// chains are.  Once every live column has switched the loop is the single kernel's post-switch
+// step: one FTL update and NT FTRL steps.
+//
+// stats[0] += (sequence, step) pairs whose switch test ran, once per step however many columns
+// needed it, up to the last undecided column's switch or horizon (not the speculated steps
+// beyond): Σ_b max_m (pre-switch steps of column m), the lane-group sweeps' re-scan count.
+#include "ocx_internal.h"
+#include "ocx_sim_kernels.h"
+
+namespace {
+
+constexpr int kColsBlock = 256;
+constexpr int kSpec = 4;     // pre-switch steps whose prefix re-scans run side by side
+constexpr int kMaxCols = 8;  // the widest instance
+
+struct WaveColsArgs {
+    const double* zt;
+    const double* yt;
+    int64_t B, T;
+    int d, P, C;
+    int64_t G;
+    const double* thresh;  // [B][M]
+    int64_t M, k0;         // row stride, first column of this launch
+    int nt;                // columns of this launch (<= the instance's NT)
+    int64_t h[kMaxCols];   // their horizons, non-decreasing in [0, T]; h[nt …] = h[nt − 1]
+    double eta0;
+    double* regret;        // [B][M]
+    int64_t* switch_step;  // [B][M], nullable
+    unsigned long long* stats;  // [2], nullable
+};
+
+// acc + v_0 + v_1 + ... + v_{n-1}, left to right (v_k = lane k's value), n <= 64.
+// The values go through the wave's LDS slot `buf`; every lane returns the same sum.
+__device__ __forceinline__ double ordered_sum(double acc, double v, int n, double* buf,
+                                              int lane) {
+    buf[lane] = v;
+    __builtin_amdgcn_wave_barrier();
+    int k = 0;
+    for (; k + 8 <= n; k += 8) {
+        double t[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) t[u] = buf[k + u];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += t[u];
+    }
+    for (; k < n; ++k) acc += buf[k];
+    __builtin_amdgcn_wave_barrier();
+    return acc;
+}
+
+// NT of those sums from 0.0 side by side: out[m] = v[m]_0 + ... + v[m]_{n-1}, each left to
+// right, the NT dependent chains interleaved through NT x 64 slots of `buf`.
+template <int NT>
+__device__ __forceinline__ void ordered_sum_cols(const double (&v)[NT], int n, double* buf,
+                                                 int lane, double (&out)[NT]) {
+#pragma unroll
+    for (int m = 0; m < NT; ++m) {
+        buf[m * 64 + lane] = v[m];
+        out[m] = 0.0;
+    }
+    __builtin_amdgcn_wave_barrier();
+    int u = 0;
+    for (; u + 4 <= n; u += 4) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+#pragma unroll
+            for (int m = 0; m < NT; ++m) out[m] += buf[m * 64 + u + w];
+    }
+    for (; u < n; ++u)
+#pragma unroll
+        for (int m = 0; m < NT; ++m) out[m] += buf[m * 64 + u];
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ double grad(double diff) {
+    return diff > 0.0 ? 0.5 : (diff < 0.0 ? -0.5 : 0.0);
+}
+
+}  // namespace
+
+template <int DMAX, int NT>
+__global__ __launch_bounds__(kColsBlock) void ocx_smart_wave_cols_kernel(WaveColsArgs a) {
+    constexpr int kBuf = kSpec > NT ? kSpec : NT;  // 64-double LDS rows per wave
+    __shared__ double bufs[kColsBlock * kBuf];
+    const int lane = threadIdx.x & 63;
+    double* buf = bufs + (threadIdx.x & ~63) * kBuf;
+    const int64_t b = (int64_t)blockIdx.x * (kColsBlock / 64) + (threadIdx.x >> 6);
+    if (b >= a.B) return;
+    const double* __restrict__ zt = a.zt;
+    const int64_t T = a.T, G = a.G;
+    const int d = a.d, P = a.P, C = a.C, nt = a.nt;
+    const double eta0 = a.eta0;
+    const int S = 64 / P;
+    const int64_t g = b / S;
+    const int s = (int)(b - g * S);
+    const bool own = lane < d;  // this lane's coordinate j = lane exists
+    // tile offset of coordinate `lane` of this sequence at step 0 (+ t·128 for step t)
+    int64_t zoff = 0;
+    if (own) {
+        const int c = lane / C, rr = lane - c * C;
+        zoff = ((int64_t)(rr >> 1) * G + g) * T * 128 + (s * P + c) * 2 + (rr & 1);
+    }
+    const double* __restrict__ yp = a.yt + g * T * S + s;  // y_t = yp[t * S]
+
+    // ½|z_i·sv − y_i| summed over rows i < n in order: lane ℓ forms the terms of rows
+    // i0 + ℓ (coordinates read from the lanes that own them), the wave adds them.  With
+    // DMAX > 0 (d <= DMAX) the next chunk's rows are loaded while this chunk is summed.
+    auto offset_of = [&](int j) -> int64_t {
+        return ((int64_t)__builtin_amdgcn_readlane((int)(zoff >> 32), j) << 32) |
+               (uint32_t)__builtin_amdgcn_readlane((int)zoff, j);
+    };
+    auto coord_of = [&](double v, int j) -> double {
+        return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j),
+                                __builtin_amdgcn_readlane(__double2loint(v), j));
+    };
+    auto prefix_loss = [&](double sv, int64_t n) -> double {
+        double tot = 0.0;
+        if constexpr (DMAX > 0) {
+            double zc[DMAX], yc = 0.0;
+            auto load = [&](int64_t i0, double (&zb)[DMAX], double& yb) {
+                const int64_t i = (i0 + lane < n) ? i0 + lane : 0;
+#pragma unroll
+                for (int j = 0; j < DMAX; ++j) zb[j] = (j < d) ? zt[offset_of(j) + i * 128] : 0.0;
+                yb = yp[i * S];
+            };
+            if (n > 0) load(0, zc, yc);
+            for (int64_t i0 = 0; i0 < n; i0 += 64) {
+                const int m = (int)((n - i0) < 64 ? (n - i0) : 64);
+                double zn[DMAX], yn = 0.0;
+                if (i0 + 64 < n) load(i0 + 64, zn, yn);
+                double q = 0.0;
+#pragma unroll
+                for (int j = 0; j < DMAX; ++j)
+                    if (j < d) q += zc[j] * coord_of(sv, j);
+                const double h = 0.5 * fabs(q - yc);
+                tot = ordered_sum(tot, h, m, buf, lane);
+#pragma unroll
+                for (int j = 0; j < DMAX; ++j) zc[j] = zn[j];
+                yc = yn;
+            }
+        } else {
+            for (int64_t i0 = 0; i0 < n; i0 += 64) {
+                const int m = (int)((n - i0) < 64 ? (n - i0) : 64);
+                const int64_t i = i0 + (lane < m ? lane : 0);
+                double q = 0.0;
+                for (int j = 0; j < d; ++j) q += zt[offset_of(j) + i * 128] * coord_of(sv, j);
+                const double h = 0.5 * fabs(q - yp[i * S]);
+                tot = ordered_sum(tot, h, m, buf, lane);
+            }
+        }
+        return tot;
+    };
+    // The prefix losses of kSpec consecutive steps t..t+K-1 at once: sv[k] = s_{t+k}, rows
+    // 0..t+k each.  The chunk's rows are shared; a row beyond t+k contributes +0.0 to
+    // chain k, which leaves that sum unchanged.  The K ordered chains interleave.
+    auto prefix_loss_multi = [&](const double (&sv)[kSpec], int64_t t, int K,
+                                 double (&out)[kSpec]) {
+#pragma unroll
+        for (int k = 0; k < kSpec; ++k) out[k] = 0.0;
+        const int64_t n = t + K;
+        auto chunk = [&](int64_t i0, const double* zr, double yr) {
+            const int m = (int)((n - i0) < 64 ? (n - i0) : 64);
+            const int64_t i = i0 + lane;
+#pragma unroll
+            for (int k = 0; k < kSpec; ++k) {
+                double q = 0.0;
+                if constexpr (DMAX > 0) {
+#pragma unroll
+                    for (int j = 0; j < DMAX; ++j)
+                        if (j < d) q += zr[j] * coord_of(sv[k], j);
+                } else {
+                    const int64_t ii = (i < n) ? i : 0;
+                    for (int j = 0; j < d; ++j) q += zt[offset_of(j) + ii * 128] * coord_of(sv[k], j);
+                }
+                buf[k * 64 + lane] = (k < K && i <= t + k) ? 0.5 * fabs(q - yr) : 0.0;
+            }
+            __builtin_amdgcn_wave_barrier();
+            int u = 0;
+            for (; u + 4 <= m; u += 4) {
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+#pragma unroll
+                    for (int k = 0; k < kSpec; ++k) out[k] += buf[k * 64 + u + v];
+            }
+            for (; u < m; ++u)
+#pragma unroll
+                for (int k = 0; k < kSpec; ++k) out[k] += buf[k * 64 + u];
+            __builtin_amdgcn_wave_barrier();
+        };
+        if constexpr (DMAX > 0) {
+            double zc[DMAX], yc = 0.0;
+            auto load = [&](int64_t i0, double (&zb)[DMAX], double& yb) {
+                const int64_t i = (i0 + lane < n) ? i0 + lane : 0;
+#pragma unroll
+                for (int j = 0; j < DMAX; ++j) zb[j] = (j < d) ? zt[offset_of(j) + i * 128] : 0.0;
+                yb = yp[i * S];
+            };
+            load(0, zc, yc);
+            for (int64_t i0 = 0; i0 < n; i0 += 64) {
+                double zn[DMAX], yn = 0.0;
+                if (i0 + 64 < n) load(i0 + 64, zn, yn);
+                chunk(i0, zc, yc);
+#pragma unroll
+                for (int j = 0; j < DMAX; ++j) zc[j] = zn[j];
+                yc = yn;
+            }
+        } else {
+            for (int64_t i0 = 0; i0 < n; i0 += 64) {
+                const int64_t i = (i0 + lane < n) ? i0 + lane : 0;
+                chunk(i0, nullptr, yp[i * S]);
+            }
+        }
+    };
+    // FTL action (fast_algorithms.py:37-49) of the state held in `th`, coordinate `lane`
+    auto action_ftl = [&](double th) -> double {
+        const double n2 = ordered_sum(0.0, own ? th * th : 0.0, d, buf, lane);
+        if (n2 == 0.0) return 0.0;
+        const double scale = -(1.0 / sqrt(n2));
+        return scale * th;
+    };
+
+    // shared by the columns
+    double tf = 0.0;  // theta_ftl (coordinate `lane`)
+    double ftl_loss = 0.0;
+    unsigned long long tested = 0;
+    // per column; spare columns (m >= nt) are never live
+    double th[NT], tr[NT], total[NT];  // threshold, theta_ftrl (coordinate `lane`), own total
+    bool switched[NT];
+    int64_t sw[NT];
+#pragma unroll
+    for (int m = 0; m < NT; ++m) {
+        th[m] = (m < nt) ? a.thresh[b * a.M + a.k0 + m] : 0.0;
+        tr[m] = total[m] = 0.0;
+        switched[m] = false;
+        sw[m] = -1;
+    }
+    // FTRL step tk (:148-154) of the NT columns side by side, on the row (z, yv) the FTL leg
+    // of that step has loaded, committed where act[m]
+    auto ftrl_steps = [&](int64_t tk, double z, double yv, const bool (&act)[NT]) {
+        const double sc = -(eta0 / sqrt((double)(tk + 1)));
+        double xr[NT], v[NT], n2[NT], pr[NT];
+#pragma unroll
+        for (int m = 0; m < NT; ++m) {
+            xr[m] = sc * tr[m];
+            v[m] = own ? xr[m] * xr[m] : 0.0;
+        }
+        ordered_sum_cols<NT>(v, d, buf, lane, n2);
+#pragma unroll
+        for (int m = 0; m < NT; ++m) {
+            if (n2[m] > 1.0) xr[m] *= 1.0 / sqrt(n2[m]);
+            v[m] = own ? z * xr[m] : 0.0;
+        }
+        ordered_sum_cols<NT>(v, d, buf, lane, pr);
+#pragma unroll
+        for (int m = 0; m < NT; ++m) {
+            if (act[m]) {
+                const double dr = pr[m] - yv;
+                total[m] += 0.5 * fabs(dr);
+                tr[m] += grad(dr) * z;
+            }
+        }
+    };
+
+    double xf_next = 0.0;  // FTL(theta_ftl) as it stands: FTL(0) = 0
+    int mf = 0;            // columns [0, mf) are frozen
+    int64_t t = 0;
+    while (mf < nt) {
+        int64_t hn = 0;  // the next horizon: h[mf]
+#pragma unroll
+        for (int m = NT - 1; m >= 0; --m)
+            if (m >= mf) hn = a.h[m];
+        if (hn == t) {
+            // the freeze of every column whose horizon is t: comparator = FTL(theta_ftl)
+            // on rows 0 … t − 1 (:162-163), once for all of them
+            const double comp = prefix_loss(action_ftl(tf), t);
+            int nf = mf;
+#pragma unroll
+            for (int m = 0; m < NT; ++m) {
+                if (m >= mf && m < nt && a.h[m] == t) {
+                    ++nf;
+                    if (lane == 0) {
+                        const int64_t o = b * a.M + a.k0 + m;
+                        // a column that never switched: total_loss is ftl_loss (:156)
+                        a.regret[o] = (switched[m] ? total[m] : ftl_loss) - comp;
+                        if (a.switch_step) a.switch_step[o] = sw[m];
+                    }
+                }
+            }
+            mf = nf;
+            continue;
+        }
+        bool live[NT];
+        bool anyun = false;
+#pragma unroll
+        for (int m = 0; m < NT; ++m) {
+            live[m] = m >= mf && m < nt;
+            anyun = anyun || (live[m] && !switched[m]);
+        }
+        if (!anyun) {
+            // every live column has switched: the single kernel's post-switch step (:140-154),
+            // FTL still updated, FTRL played with each column's own theta
+            const double z = own ? zt[zoff + t * 128] : 0.0;
+            const double yv = yp[t * S];
+            const double xf = action_ftl(tf);
+            const double pf = ordered_sum(0.0, own ? z * xf : 0.0, d, buf, lane);
+            const double dfl = pf - yv;
+            tf += grad(dfl) * z;
+            ftl_loss += 0.5 * fabs(dfl);
+            ftrl_steps(t, z, yv, live);
+            ++t;
+            continue;
+        }
+        // Pre-switch steps go kSpec at a time: the FTL part of each step (which never depends
+        // on the switch) runs ahead, the kSpec prefix re-scans run side by side, and the
+        // switch test is then applied per column in step order.
+        const int K = (hn - t) < kSpec ? (int)(hn - t) : kSpec;
+        double sv[kSpec], fl[kSpec], zk[kSpec], yk[kSpec];
+#pragma unroll
+        for (int k = 0; k < kSpec; ++k) {
+            sv[k] = 0.0;
+            fl[k] = 0.0;
+            zk[k] = yk[k] = 0.0;
+            if (k < K) {
+                const double z = zk[k] = own ? zt[zoff + (t + k) * 128] : 0.0;
+                const double yv = yk[k] = yp[(t + k) * S];
+                const double pf = ordered_sum(0.0, own ? z * xf_next : 0.0, d, buf, lane);
+                const double dfl = pf - yv;
+                tf += grad(dfl) * z;
+                ftl_loss += 0.5 * fabs(dfl);
+                fl[k] = ftl_loss;
+                sv[k] = action_ftl(tf);  // s_{t+k} (:157); also the next step's FTL action
+                xf_next = sv[k];
+            }
+        }
+        double sl[kSpec];
+        prefix_loss_multi(sv, t, K, sl);
+        bool before[NT];  // switched before this group
+        int ks[NT];       // the group's step at which the column switches, or -1
+        int steps = 0;    // steps of the group whose test some column needed
+#pragma unroll
+        for (int m = 0; m < NT; ++m) {
+            before[m] = live[m] && switched[m];
+            ks[m] = -1;
+            if (live[m] && !switched[m]) {
+#pragma unroll
+                for (int k = 0; k < kSpec; ++k) {
+                    if (k < K && ks[m] < 0 && fl[k] - sl[k] >= th[m]) {
+                        ks[m] = k;
+                        total[m] = fl[k];  // the additions of `total_loss += lf` so far (:156)
+                    }
+                }
+                if (ks[m] >= 0) {
+                    switched[m] = true;
+                    sw[m] = t + ks[m];
+                }
+                const int c = ks[m] >= 0 ? ks[m] + 1 : K;
+                steps = c > steps ? c : steps;
+            }
+        }
+        tested += (unsigned long long)steps;
+        // FTRL on the group's steps: all of them for a column switched before the group, the
+        // steps after its switch for one that switched inside it
+#pragma unroll 1
+        for (int k = 0; k < K; ++k) {  // one copy of the step: the row is picked by selects
+            bool act[NT];
+            bool any = false;
+#pragma unroll
+            for (int m = 0; m < NT; ++m) {
+                act[m] = before[m] || (ks[m] >= 0 && k > ks[m]);
+                any = any || act[m];
+            }
+            double z = zk[0], yv = yk[0];
+#pragma unroll
+            for (int u = 1; u < kSpec; ++u) {
+                z = (k == u) ? zk[u] : z;
+                yv = (k == u) ? yk[u] : yv;
+            }
+            if (any) ftrl_steps(t + k, z, yv, act);
+        }
+        t += K;
+    }
+    if (lane == 0 && a.stats && tested) atomicAdd(&a.stats[0], tested);
+}
+
+namespace {
+
+template <int NT>
+hipError_t launch_cols(const WaveColsArgs& a, hipStream_t st) {
+    const unsigned grid = (unsigned)((a.B + (kColsBlock / 64) - 1) / (kColsBlock / 64));
+    if (a.d <= 8)
+        hipLaunchKernelGGL((ocx_smart_wave_cols_kernel<8, NT>), dim3(grid), dim3(kColsBlock), 0,
+                           st, a);
+    else
+        hipLaunchKernelGGL((ocx_smart_wave_cols_kernel<0, NT>), dim3(grid), dim3(kColsBlock), 0,
+                           st, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+bool ocx_smart_wave_cols_instance(int group) {
+    return group == 1 || group == 2 || group == 4 || group == 8;
+}
+
+// The dispatcher's group: the smallest instance that holds M columns, capped at the widest.
+// Measured (profiles/smart_wave_cols_ab.jsonl) on 2 048 and 32 768 x 1e3
+// batches at d = 5, 16, 32 and 64 with M = 2, 4 and 7: the widest group that M fills was the
+// fastest or within 1 % of it everywhere but at d = 16 and 32 with M = 2, where a column that
+// switches at step 3 beside one that never does made group 1 5-6 % faster than group 2 (the
+// switched column's FTRL steps lengthen every group of the other's re-scan).  The shared
+// group stays: it costs max_m (pre-switch steps of m) where group 1 costs their sum, so what
+// it can lose is that margin and what group 1 can lose is a factor of M.
+int ocx_smart_wave_cols_group(const ocx_layout* L, int64_t M) {
+    (void)L;
+    int g = kMaxCols;
+    while (g > 1 && g / 2 >= M) g /= 2;
+    return g;
+}
+
+// Where the dispatcher takes this form (same measurements): up to d = 32 it was faster than
+// the lane-group sweep and than M single calls, beyond their min-max spread, at every M.  At
+// d = 64 on 2 048 sequences one pass costs what the single wave call costs (the row path above
+// d = 8 reads 64 coordinates per term) and the lane-group sweep is faster than that, so the
+// wave form wins only where it saves passes: above the lane-group sweep's widest group, 4.
+// 32 < d < 64 was not measured and follows d = 64.
+bool ocx_smart_wave_cols_worth(const ocx_layout* L, int64_t M) {
+    return L->d <= 32 || M > 4;
+}
+
+hipError_t ocx_launch_smart_wave_cols(const ocx_layout* L, const double* zt, const double* yt,
+                                      const int64_t* hz, const double* th, int64_t M, double eta0,
+                                      double* reg, int64_t* sw, unsigned long long* stats,
+                                      int group, hipStream_t st) {
+    if (L->B == 0 || M <= 0) return hipSuccess;
+    if (L->d > 64) return hipErrorNotSupported;
+    if (!ocx_smart_wave_cols_instance(group)) return hipErrorInvalidValue;
+    WaveColsArgs a{zt, yt, L->B, L->T, (int)L->d, L->P, L->C, L->G, th, M, /*k0*/ 0, /*nt*/ 0,
+                   {0, 0, 0, 0, 0, 0, 0, 0}, eta0, reg, sw, stats};  // k0, nt, h: per launch
+    for (int64_t k0 = 0; k0 < M; k0 += group) {
+        const int nt = (int)(M - k0 < group ? M - k0 : group);
+        a.k0 = k0;
+        a.nt = nt;
+        for (int m = 0; m < kMaxCols; ++m) a.h[m] = hz ? hz[k0 + (m < nt ? m : nt - 1)] : L->T;
+        // the smallest instance that holds them
+        const hipError_t e = nt <= 1   ? launch_cols<1>(a, st)
+                             : nt <= 2 ? launch_cols<2>(a, st)
+                             : nt <= 4 ? launch_cols<4>(a, st)
+                                       : launch_cols<8>(a, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}

@@ -62,8 +62,10 @@ def case_regrets(title: str, T: int, g_emp_T: float, *, runs: int, replicates: i
     out = {}
     out["FTRL"] = db.simulate_alg(0, SQRT2).clone()
     out["FTL"] = db.simulate_alg(1, SQRT2).clone()
-    out["SMART"] = db.simulate_smart(math.sqrt(2 * T), SQRT2).clone()
-    out["EMP"] = db.simulate_smart(float(g_emp_T), SQRT2).clone()
+    # SMART and EMP share their FTL leg and every prefix re-scan up to the later switch: one
+    # two-column sweep, the bits of two simulate_smart launches
+    both = db.simulate_smart_thresholds([math.sqrt(2 * T), float(g_emp_T)], SQRT2)["regret"]
+    out["SMART"], out["EMP"] = both[:, 0], both[:, 1]
     return {k: v[:B].cpu().numpy().reshape(runs, replicates) for k, v in out.items()}
 
 

@@ -206,9 +206,12 @@ def simulate_smart_thresholds_batch(z, y, thresholds, eta0: float = SQRT2, *,
     group of them (ocx_simulate_smart_thresholds_batch): one FTL trajectory, one prefix test
     and one comparator per pass, a switch step and an FTRL state per column.
 
-    Column m is simulate_smart_batch's lane-group kernel with thresh = thresholds[..., m]: in
-    the bit-exact modes (lanes_per_seq 1 / -k) the reference's prefix re-scan and streamed
-    comparator, bit for bit; in the others both closed forms.  ``thresh = +inf`` makes a
+    Column m is simulate_smart_batch with thresh = thresholds[..., m]: in the bit-exact modes
+    (lanes_per_seq 1 / -k) the reference's prefix re-scan and streamed comparator, bit for
+    bit — run by the one-wave-per-sequence kernel (ocx_smart_wave_cols.hip, one re-scan per
+    step for up to eight columns) at d <= 64 and B <= 32768, by the lane-group kernel
+    elsewhere or under ``OCX_SMART_KERNEL=lanes``; in the other modes the lane-group kernel
+    with both closed forms.  ``thresh = +inf`` makes a
     column FTL's regret, with the same adds and the same comparator; ``sqrt(2T)`` and the
     empirical g(T) are the drivers' SMART and EMP.  Returns regret [B, M] or, with
     ``return_switch``, (regret, switch_step [B, M] int64, -1 = never)."""
@@ -268,10 +271,11 @@ def simulate_smart_curve_batch(z, y, horizons, thresholds=None, eta0: float = SQ
     stopping at the group's last horizon (ocx_simulate_smart_curve_batch).
 
     ``horizons`` [K]: integers, non-decreasing in [0, T]; ``thresholds`` [K] or [B, K]
-    (None: SMART's own sqrt(2 t_k)).  Column k is simulate_smart_batch's lane-group kernel on
+    (None: SMART's own sqrt(2 t_k)).  Column k is simulate_smart_batch on
     (z[:, :t_k], y[:, :t_k]) with thresh = thresholds[..., k]: bit for bit in the bit-exact
-    modes (lanes_per_seq 1 / -k: the reference's prefix re-scan and streamed comparator), both
-    closed forms in the others.  Returns regret [B, K] or, with ``return_switch``, (regret,
+    modes (lanes_per_seq 1 / -k: the reference's prefix re-scan and streamed comparator; the
+    one-wave-per-sequence kernel where simulate_smart_thresholds_batch says it runs), the
+    lane-group kernel with both closed forms in the others.  Returns regret [B, K] or, with ``return_switch``, (regret,
     switch_step [B, K] int64, in [0, t_k) or -1 = never)."""
     z = _f64(z)
     y = _f64(y)
@@ -830,11 +834,15 @@ class DeviceBatch:
     def simulate_smart_thresholds(self, thresholds, eta0: float = SQRT2, *,
                                   closed_prefix: Optional[bool] = None,
                                   closed_comparator: Optional[bool] = None, stats=None,
-                                  _group=None):
+                                  _group=None, _wave=None):
         """Threshold sweep of the resident batch (ocx_dev_simulate_smart_thresholds, async):
         SMART for every switch threshold of ``thresholds`` ([M], or [B, M] per sequence;
         validated here, NaN and ±inf are legal), each pass over z serving
-        ocx_smart_thresholds_group(L, M) of them.  Returns device tensors ``regret`` [B, M]
+        ocx_smart_thresholds_group(L, M) of them.  In a bit-exact layout, in the re-scan mode
+        (both flags off) without ``stats``, at d <= 64 and B <= 32768 the call runs the
+        one-wave-per-sequence kernel (ocx_smart_wave_cols.hip: one prefix re-scan per step for
+        up to eight columns; the same bits), elsewhere the lane-group kernel;
+        ``OCX_SMART_KERNEL=lanes`` holds it on the latter.  Returns device tensors ``regret`` [B, M]
         float64 and ``switch_step`` [B, M] int64 (-1 = never); column m is what
         simulate_smart(thresholds[..., m], eta0, stats=...) gives, bit for bit in the same
         layout.  ``thresh = +inf`` makes a column FTL's regret, with the same adds and the same
@@ -843,11 +851,15 @@ class DeviceBatch:
         ([2] int64 device tensor, optional) accumulates, per pass, the (sequence, step) pairs
         that re-scanned — once per step however many columns needed it — and the sequences
         that took the closed comparator.  (``_group``: tests and tools/thresholds_probe.py
-        force the group size through include/ocx_testing.h.)"""
+        force the group size through include/ocx_testing.h; ``_wave``: tests and
+        tools/smart_wave_cols_probe.py force the one-wave-per-sequence kernel with that group
+        size, 1, 2, 4 or 8, in any layout — re-scan mode only.)"""
         torch = self.torch
         B = int(self.L.B)
         tha = _thresholds(thresholds, B)
         M = int(tha.shape[1])
+        if _wave is not None and (closed_prefix or closed_comparator or _group is not None):
+            raise ValueError("_wave runs the re-scan mode only, and excludes _group")
         if closed_prefix is None:
             closed_prefix = not self.exact
         if closed_comparator is None:
@@ -862,7 +874,10 @@ class DeviceBatch:
                 M, float(eta0), out["regret"].data_ptr() if B * M else None,
                 out["switch_step"].data_ptr() if B * M else None, flags,
                 stats.data_ptr() if stats is not None else None)
-        if _group is None:
+        if _wave is not None:
+            self._call("ocx_test_simulate_smart_wave_cols", *args[:3], None, *args[3:8], args[9],
+                       int(_wave), self._sp)
+        elif _group is None:
             self._call("ocx_dev_simulate_smart_thresholds", *args, self._sp)
         else:
             self._call("ocx_test_simulate_smart_thresholds", *args, int(_group), self._sp)
@@ -872,10 +887,11 @@ class DeviceBatch:
     def simulate_smart_curve(self, horizons, thresholds=None, eta0: float = SQRT2, *,
                              closed_prefix: Optional[bool] = None,
                              closed_comparator: Optional[bool] = None, stats=None,
-                             _group=None):
+                             _group=None, _wave=None):
         """SMART regret curves of the resident batch (ocx_dev_simulate_smart_curve, async):
         SMART for K pairs (horizon t_k, threshold), each pass over z serving
         ocx_smart_curve_group(L, K) consecutive pairs and stopping at their last horizon.
+        The one-wave-per-sequence kernel runs where simulate_smart_thresholds says it does.
         ``horizons`` [K]: integers, non-decreasing in [0, T] (validated here; equal horizons
         are legal); ``thresholds`` [K] or [B, K] (validated through _thresholds; None: SMART's
         own sqrt(2 t_k)).  Returns device tensors ``regret`` [B, K] float64 and ``switch_step``
@@ -886,12 +902,15 @@ class DeviceBatch:
         column) by that column's first t_k steps.  ``stats`` ([2] int64 device tensor,
         optional) accumulates, per pass, the (sequence, step) pairs that re-scanned and the
         (sequence, column) pairs that took the closed comparator.  (``_group``: tests and
-        tools/smart_curve_probe.py force the group size through include/ocx_testing.h.)"""
+        tools/smart_curve_probe.py force the group size through include/ocx_testing.h;
+        ``_wave``: as in simulate_smart_thresholds.)"""
         torch = self.torch
         B = int(self.L.B)
         hz = _horizons(horizons, self.L.T)
         tha = _smart_curve_thresholds(thresholds, hz, B)
         K = int(hz.size)
+        if _wave is not None and (closed_prefix or closed_comparator or _group is not None):
+            raise ValueError("_wave runs the re-scan mode only, and excludes _group")
         if closed_prefix is None:
             closed_prefix = not self.exact
         if closed_comparator is None:
@@ -907,7 +926,10 @@ class DeviceBatch:
                 out["regret"].data_ptr() if B * K else None,
                 out["switch_step"].data_ptr() if B * K else None, flags,
                 stats.data_ptr() if stats is not None else None)
-        if _group is None:
+        if _wave is not None:
+            self._call("ocx_test_simulate_smart_wave_cols", *args[:9], args[10], int(_wave),
+                       self._sp)
+        elif _group is None:
             self._call("ocx_dev_simulate_smart_curve", *args, self._sp)
         else:
             self._call("ocx_test_simulate_smart_curve", *args, int(_group), self._sp)
