@@ -595,7 +595,7 @@ int ocx_smart_thresholds_group(const ocx_layout* L, int64_t M) {
 // The sweeps' one-wave-per-sequence form (ocx_smart_wave_cols.hip) is taken, with the group
 // unforced, in the re-scan mode without a stats tensor, in the exact layouts (in a butterfly
 // layout its reference-order sums are not the lane-group instance's bits) and at the single
-// call's own sizes (ocx_launch_smart), where the measurements found it faster than both the
+// call's own sizes (ocx_smart_wave_sizes), where the measurements found it faster than both the
 // lane-group sweep and M single calls (ocx_smart_wave_cols_worth).  OCX_SMART_KERNEL=lanes
 // holds the sweeps on the lane-group kernel, as it does the single call; =wave takes the wave
 // form wherever the rest of the rule allows it, measured faster or not.
@@ -603,7 +603,7 @@ static bool smart_sweep_takes_wave(const ocx_layout* L, int64_t M, int flags, co
                                    int group) {
     if (group != 0 || flags != 0 || stats) return false;
     if (!(L->chain || L->P == 1)) return false;
-    if (L->d > 64 || L->B > 32768) return false;
+    if (!ocx_smart_wave_sizes(L)) return false;
     if (const char* e = std::getenv("OCX_SMART_KERNEL")) return std::strcmp(e, "wave") == 0;
     return ocx_smart_wave_cols_worth(L, M);
 }

@@ -572,10 +572,9 @@ hipError_t ocx_launch_smart(const ocx_layout* L, const double* zt, const double*
                             const double* th, double eta0, double* reg, int64_t* sw,
                             hipStream_t st) {
     if (L->G == 0) return hipSuccess;
-    // Small batches (the drivers' few hundred sequences) cannot hide the prefix
-    // re-scan's latency with lane groups: one wavefront per sequence instead.
-    // OCX_SMART_KERNEL=wave|lanes forces a path (tests, tuning).
-    bool wave = L->d <= 64 && L->B <= 32768;  // measured: wave 0.22 s vs lanes 0.30 s at 32768 (d = 5)
+    // One wavefront per sequence at the sizes where that was measured faster
+    // (ocx_smart_wave_sizes).  OCX_SMART_KERNEL=wave|lanes forces a path (tests, tuning).
+    bool wave = ocx_smart_wave_sizes(L);
     if (const char* e = std::getenv("OCX_SMART_KERNEL"))
         wave = std::strcmp(e, "wave") == 0 && L->d <= 64;
     if (wave) return ocx_launch_smart_wave(L, zt, yt, th, eta0, reg, sw, st);

@@ -157,7 +157,9 @@ hipError_t ocx_launch_smart_curve(const ocx_layout* L, const double* zt, const d
                                   const int64_t* hz, const double* th, int64_t K, double eta0,
                                   double* reg, int64_t* sw, int closed_prefix, int closed_comp,
                                   unsigned long long* stats, int group, hipStream_t st);
-// SMART with one wavefront per sequence (ocx_smart_wave.hip), d <= 64
+// SMART with one wavefront per sequence (ocx_smart_wave.hip), d <= 64.  ocx_smart_wave_sizes:
+// the sizes at which ocx_launch_smart takes it, and the sweeps' dispatch its column form.
+bool ocx_smart_wave_sizes(const ocx_layout* L);
 hipError_t ocx_launch_smart_wave(const ocx_layout* L, const double* zt, const double* yt,
                                  const double* th, double eta0, double* reg, int64_t* sw,
                                  hipStream_t st);

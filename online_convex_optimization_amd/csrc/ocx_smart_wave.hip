@@ -9,37 +9,15 @@
 // once (their dot products are independent) and the wave adds them to the running
 // sum in order from LDS, so only the additions themselves stay sequential — the
 // reference's own summation order, bit for bit.  Lane j < d keeps coordinate j of the
-// FTL and FTRL states; the d-term sums of the actions use the same ordered adder.
+// FTL and FTRL states; the d-term sums of the actions use the same ordered adder
+// (ocx_smart_wave.h, shared with the NT-column form in ocx_smart_wave_cols.hip).
 #include "ocx_internal.h"
 #include "ocx_sim_kernels.h"
+#include "ocx_smart_wave.h"
 
 namespace {
 
 constexpr int kSmartBlock = 256;
-constexpr int kSpec = 4;  // pre-switch steps whose prefix re-scans run side by side
-
-// acc + v_0 + v_1 + ... + v_{n-1}, left to right (v_k = lane k's value), n <= 64.
-// The values go through the wave's LDS slot `buf`; every lane returns the same sum.
-__device__ __forceinline__ double ordered_sum(double acc, double v, int n, double* buf,
-                                              int lane) {
-    buf[lane] = v;
-    __builtin_amdgcn_wave_barrier();
-    int k = 0;
-    for (; k + 8 <= n; k += 8) {
-        double t[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t[u] = buf[k + u];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc += t[u];
-    }
-    for (; k < n; ++k) acc += buf[k];
-    __builtin_amdgcn_wave_barrier();
-    return acc;
-}
-
-__device__ __forceinline__ double grad(double diff) {
-    return diff > 0.0 ? 0.5 : (diff < 0.0 ? -0.5 : 0.0);
-}
 
 }  // namespace
 
@@ -175,13 +153,6 @@ __global__ __launch_bounds__(kSmartBlock) void ocx_smart_wave_kernel(
             }
         }
     };
-    // FTL action (fast_algorithms.py:37-49) of the state held in `th`, coordinate `lane`
-    auto action_ftl = [&](double th) -> double {
-        const double n2 = ordered_sum(0.0, own ? th * th : 0.0, d, buf, lane);
-        if (n2 == 0.0) return 0.0;
-        const double scale = -(1.0 / sqrt(n2));
-        return scale * th;
-    };
 
     double tf = 0.0, tr = 0.0;  // theta_ftl, theta_ftrl (coordinate `lane`)
     bool switched = false;
@@ -191,7 +162,7 @@ __global__ __launch_bounds__(kSmartBlock) void ocx_smart_wave_kernel(
     auto post_switch_step = [&](int64_t t) {
         const double z = own ? zt[zoff + t * 128] : 0.0;
         const double yv = yp[t * S];
-        const double xf = action_ftl(tf);
+        const double xf = action_ftl(tf, d, buf, lane);
         const double pf = ordered_sum(0.0, own ? z * xf : 0.0, d, buf, lane);
         const double dfl = pf - yv;
         tf += grad(dfl) * z;
@@ -232,7 +203,7 @@ __global__ __launch_bounds__(kSmartBlock) void ocx_smart_wave_kernel(
                 lf[k] = 0.5 * fabs(dfl);
                 ftl_loss += lf[k];
                 fl[k] = ftl_loss;
-                sv[k] = action_ftl(tf);  // s_{t+k} (:157); also the next step's FTL action
+                sv[k] = action_ftl(tf, d, buf, lane);  // s_{t+k} (:157), the next FTL action
                 xf_next = sv[k];
             }
         }
@@ -266,12 +237,18 @@ __global__ __launch_bounds__(kSmartBlock) void ocx_smart_wave_kernel(
         t += K;
     }
     // final comparator = FTL(theta_ftl) (:162-163)
-    const double comp = prefix_loss(action_ftl(tf), T);
+    const double comp = prefix_loss(action_ftl(tf, d, buf, lane), T);
     if (lane == 0) {
         regret[b] = total_loss - comp;
         if (switch_step) switch_step[b] = sw;
     }
 }
+
+// Where the single call takes this kernel, and the sweeps their column form of it.  Small
+// batches (the drivers' few hundred sequences) cannot hide the prefix re-scan's latency with
+// lane groups; measured up to the batch that fills the device: wave 0.22 s vs lanes 0.30 s at
+// 32768 x 1e3 (d = 5).
+bool ocx_smart_wave_sizes(const ocx_layout* L) { return L->d <= 64 && L->B <= 32768; }
 
 hipError_t ocx_launch_smart_wave(const ocx_layout* L, const double* zt, const double* yt,
                                  const double* th, double eta0, double* reg, int64_t* sw,

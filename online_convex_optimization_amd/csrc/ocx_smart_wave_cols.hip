@@ -9,10 +9,13 @@
 // (kSpec steps ahead), one prefix_loss_multi per speculated group and one comparator scan per
 // distinct horizon exist once per sequence.
 //
-// The summation pieces — ordered_sum, prefix_loss, prefix_loss_multi with its DMAX = 8 and
-// DMAX = 0 row paths, the tile addressing by readlane — are ocx_smart_wave_kernel's, operation
-// for operation, written out a second time (that kernel stays as it is).  They add in the
-// reference's order whatever the layout, so every column carries the C oracle's bits.
+// The summation pieces are ocx_smart_wave_kernel's.  The ordered adder, the sub-gradient and
+// the FTL action are one copy, in ocx_smart_wave.h; prefix_loss, prefix_loss_multi with its
+// DMAX = 8 and DMAX = 0 row paths and the tile addressing by readlane are that kernel's
+// operation for operation, written out a second time here (shared, they change the device
+// assembly; and the single call stays on its own kernel, whose speed after the switch the
+// one-column instance does not reach: DESIGN.md §3.13).  They add in the reference's order
+// whatever the layout, so every column carries the C oracle's bits.
 //
 // Columns.  Column m of a launch is (h[m], th[b][k0 + m]); the horizons are non-decreasing, so
 // the frozen columns are always a prefix [0, mf) of the launch and the next horizon is h[mf].
@@ -35,11 +38,11 @@
 // beyond): Σ_b max_m (pre-switch steps of column m), the lane-group sweeps' re-scan count.
 #include "ocx_internal.h"
 #include "ocx_sim_kernels.h"
+#include "ocx_smart_wave.h"
 
 namespace {
 
 constexpr int kColsBlock = 256;
-constexpr int kSpec = 4;     // pre-switch steps whose prefix re-scans run side by side
 constexpr int kMaxCols = 8;  // the widest instance
 
 struct WaveColsArgs {
@@ -57,25 +60,6 @@ struct WaveColsArgs {
     int64_t* switch_step;  // [B][M], nullable
     unsigned long long* stats;  // [2], nullable
 };
-
-// acc + v_0 + v_1 + ... + v_{n-1}, left to right (v_k = lane k's value), n <= 64.
-// The values go through the wave's LDS slot `buf`; every lane returns the same sum.
-__device__ __forceinline__ double ordered_sum(double acc, double v, int n, double* buf,
-                                              int lane) {
-    buf[lane] = v;
-    __builtin_amdgcn_wave_barrier();
-    int k = 0;
-    for (; k + 8 <= n; k += 8) {
-        double t[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t[u] = buf[k + u];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc += t[u];
-    }
-    for (; k < n; ++k) acc += buf[k];
-    __builtin_amdgcn_wave_barrier();
-    return acc;
-}
 
 // NT of those sums from 0.0 side by side: out[m] = v[m]_0 + ... + v[m]_{n-1}, each left to
 // right, the NT dependent chains interleaved through NT x 64 slots of `buf`.
@@ -99,10 +83,6 @@ __device__ __forceinline__ void ordered_sum_cols(const double (&v)[NT], int n, d
 #pragma unroll
         for (int m = 0; m < NT; ++m) out[m] += buf[m * 64 + u];
     __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ double grad(double diff) {
-    return diff > 0.0 ? 0.5 : (diff < 0.0 ? -0.5 : 0.0);
 }
 
 }  // namespace
@@ -240,13 +220,6 @@ __global__ __launch_bounds__(kColsBlock) void ocx_smart_wave_cols_kernel(WaveCol
             }
         }
     };
-    // FTL action (fast_algorithms.py:37-49) of the state held in `th`, coordinate `lane`
-    auto action_ftl = [&](double th) -> double {
-        const double n2 = ordered_sum(0.0, own ? th * th : 0.0, d, buf, lane);
-        if (n2 == 0.0) return 0.0;
-        const double scale = -(1.0 / sqrt(n2));
-        return scale * th;
-    };
 
     // shared by the columns
     double tf = 0.0;  // theta_ftl (coordinate `lane`)
@@ -301,7 +274,7 @@ __global__ __launch_bounds__(kColsBlock) void ocx_smart_wave_cols_kernel(WaveCol
         if (hn == t) {
             // the freeze of every column whose horizon is t: comparator = FTL(theta_ftl)
             // on rows 0 … t − 1 (:162-163), once for all of them
-            const double comp = prefix_loss(action_ftl(tf), t);
+            const double comp = prefix_loss(action_ftl(tf, d, buf, lane), t);
             int nf = mf;
 #pragma unroll
             for (int m = 0; m < NT; ++m) {
@@ -330,7 +303,7 @@ __global__ __launch_bounds__(kColsBlock) void ocx_smart_wave_cols_kernel(WaveCol
             // FTL still updated, FTRL played with each column's own theta
             const double z = own ? zt[zoff + t * 128] : 0.0;
             const double yv = yp[t * S];
-            const double xf = action_ftl(tf);
+            const double xf = action_ftl(tf, d, buf, lane);
             const double pf = ordered_sum(0.0, own ? z * xf : 0.0, d, buf, lane);
             const double dfl = pf - yv;
             tf += grad(dfl) * z;
@@ -357,7 +330,7 @@ __global__ __launch_bounds__(kColsBlock) void ocx_smart_wave_cols_kernel(WaveCol
                 tf += grad(dfl) * z;
                 ftl_loss += 0.5 * fabs(dfl);
                 fl[k] = ftl_loss;
-                sv[k] = action_ftl(tf);  // s_{t+k} (:157); also the next step's FTL action
+                sv[k] = action_ftl(tf, d, buf, lane);  // s_{t+k} (:157), the next FTL action
                 xf_next = sv[k];
             }
         }

@@ -1,12 +1,15 @@
 """The one-wave-per-sequence form of the two SMART sweeps (ocx_smart_wave_cols_kernel, through
 ocx_test_simulate_smart_wave_cols = DeviceBatch.simulate_smart_thresholds / simulate_smart_curve
-with ``_wave=group``, and through the product dispatch in the exact layouts).
+with ``_wave=group``, and through the product dispatch in the exact layouts), and the
+single-threshold call on the kernel it was written from (ocx_smart_wave_kernel, under
+OCX_SMART_KERNEL=wave), with which it shares its ordered adder (csrc/ocx_smart_wave.h).
 
 The kernel adds in the reference's order whatever the layout, so every comparison is
 np.array_equal on regrets and switch steps against the C oracle (or, where a case says so,
 against the existing single-threshold call): this mode is bit-exact or wrong, there are no
-tolerances.  Inputs: tests/_thresholds_cases.py, tests/_smart_curve_cases.py and
-tests/_smart_wave_cols_cases.py (conditions asserted in tests/test_smart_wave_cols_cpu.py)."""
+tolerances.  Inputs: tests/_thresholds_cases.py, tests/_smart_curve_cases.py,
+tests/_smart_wave_cols_cases.py and tests/_smart_wave_single_cases.py (conditions asserted in
+tests/test_smart_wave_cols_cpu.py)."""
 import ctypes
 import math
 
@@ -16,6 +19,7 @@ import pytest
 from oracle import oracle as O
 from tests import _smart_curve_cases as CC
 from tests import _smart_wave_cols_cases as W
+from tests import _smart_wave_single_cases as S
 from tests import _thresholds_cases as C
 
 pytestmark = pytest.mark.gpu
@@ -233,6 +237,32 @@ def test_public_calls_in_exact_layouts(eng, monkeypatch, P, d, name):
             mp.setenv("OCX_SMART_KERNEL", "lanes")   # read at every call
             held = host(run())
         assert all(np.array_equal(pub[k], held[k]) for k in pub), (P, d, name, what, "env")
+
+
+# ------------------------------------------------------------------ 8. the single call
+@pytest.mark.parametrize("Tn", S.HORIZONS)
+@pytest.mark.parametrize("d", S.DIMS)
+def test_single_call_equals_the_oracle(eng, monkeypatch, d, Tn):
+    """simulate_smart under OCX_SMART_KERNEL=wave (ocx_launch_smart_wave:
+    ocx_smart_wave_kernel<8> at d = 8, <0> at d = 9) with per-sequence thresholds, with and
+    without a switch_step tensor.  tests/test_smart_wave_cols_cpu.py asserts that the
+    oracle's switch steps at T = 67 hit every position of a speculated group, the last group
+    and -1."""
+    import torch
+    z, y, th = S.inputs(d)
+    want_reg, want_sw = S.oracle(d, Tn)
+    z, y = np.ascontiguousarray(z[:, :Tn]), np.ascontiguousarray(y[:, :Tn])
+    monkeypatch.setenv("OCX_SMART_KERNEL", "wave")   # read at every call
+    for P in S.LAYOUTS:
+        db = packed(eng, z, y, P)
+        sw = torch.full((S.B,), -7, dtype=torch.int64, device=db.device)
+        for sw_arg in (sw, None):
+            db.regret.fill_(7.0)
+            reg = db.simulate_smart(th, SQ2, switch_step=sw_arg, closed_prefix=False,
+                                    closed_comparator=False)
+            torch.cuda.synchronize()
+            assert np.array_equal(reg[:S.B].cpu().numpy(), want_reg), (d, Tn, P, sw_arg is None)
+        assert np.array_equal(sw.cpu().numpy(), want_sw), (d, Tn, P)
 
 
 def test_argument_checks(eng):

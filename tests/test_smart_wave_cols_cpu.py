@@ -1,5 +1,6 @@
 """CPU checks for the one-wave-per-sequence SMART sweeps (NumPy, the C oracle and the ABI
-only): the inputs of tests/test_gpu_smart_wave_cols.py do what that file needs, and
+only): the inputs of tests/test_gpu_smart_wave_cols.py (the sweeps' and, from
+tests/_smart_wave_single_cases.py, the single call's) do what that file needs, and
 include/ocx_testing.h declares ocx_test_simulate_smart_wave_cols with the argument list
 _lib.py binds.
 
@@ -16,6 +17,7 @@ import pytest
 from oracle import oracle as O
 from online_convex_optimization_amd import _lib
 from tests import _smart_wave_cols_cases as W
+from tests import _smart_wave_single_cases as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -43,6 +45,27 @@ def test_mid_horizons_cut_the_switch_steps_in_two(d):
     # +inf on the whole rows is FTL
     ftl = O.simulate_alg_batch(f.z, f.y, 1, W.SQ2, nthreads=4)[0]
     assert np.all(sw[:, K - 1] == -1) and np.array_equal(reg[:, K - 1], ftl)
+
+
+@pytest.mark.parametrize("d", S.DIMS)
+def test_single_call_switches_at_every_position_of_a_group(d):
+    """What the single-threshold wave test needs of its inputs, from the oracle alone: at
+    T = 67 the switch steps hit every position of a group of four speculated steps, the last
+    (partial) group and -1; the shorter horizons run the same rows."""
+    assert S.DIMS == (8, 9) and S.HORIZONS == (1, 3, 64, 67) and S.B % 4 and 24 <= S.B <= 48
+    assert set(S.LAYOUTS) == {1, -1, -4, 8}
+    z, y, th = S.inputs(d)
+    assert z.shape == (S.B, 67, d) and y.shape == (S.B, 67) and len(set(th.tolist())) == S.B
+    sw = S.oracle(d, 67)[1]
+    on = sw[sw >= 0]
+    print("switch steps", d, sorted(sw.tolist()))
+    assert set((on % 4).tolist()) == {0, 1, 2, 3}, d
+    assert np.any(on >= 64) and np.all(on < 67) and np.any(sw == -1), d
+    # a truncated run switches where the full run does, if it gets there
+    for T in S.HORIZONS[:-1]:
+        reg_t, sw_t = S.oracle(d, T)
+        assert reg_t.shape == sw_t.shape == (S.B,)
+        assert np.array_equal(sw_t, np.where(sw < T, sw, -1)), (d, T)
 
 
 def test_mid_horizons_sit_on_the_kernels_edges():
