@@ -383,7 +383,8 @@ __device__ __forceinline__ void ocx_action_exact_poly(const double (&th)[C], dou
 }
 
 // Prefixes where the closed form's maximiser of x·S_t is not unique AND the general solver's
-// answer — the central path's limit, the analytic centre of the optimal face
+// answer — the central path's limit, the analytic centre of the optimal face, approached to
+// about 1e-6
 // (ocx_exact_ball.hip), what interior-point cvxpy backends approach — is not the closed
 // form's point:
 //   l1    two or more coordinates attain max_j |S_j| > 0 (the face is their simplex; the

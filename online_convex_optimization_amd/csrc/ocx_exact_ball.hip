@@ -17,13 +17,14 @@
 // the central path from μ = 1 down to 1e-10 (μ /= 10 once λ < 1); the path's limit is the
 // analytic centre of the optimal face — the point interior-point solvers such as the ECOS /
 // Clarabel backends cvxpy picks approach — so where the minimiser is not unique this
-// returns that point.
+// returns that point to about 1e-6 (fp64 stops resolving the face's directions near
+// μ = 2e-7, see spd_solve; measured per face and tier in DESIGN.md §3.6).
 //
 // One wavefront per problem (sequence b, prefix length n): lanes stride the rows of a
 // Newton pass (gradient and Hessian sums; the rows stay in L2 across the ≈50 passes), a
 // butterfly gives every lane the same totals, and every lane solves the small system
-// redundantly (Jacobi-scaled Cholesky, pivots floored at 1e-13 for the μ → 0
-// ill-conditioning), so the control flow stays wave-uniform.  Problems are issued longest
+// redundantly (Jacobi-scaled Cholesky; a pivot under 1e-13, the μ → 0 ill-conditioning,
+// takes no step), so the control flow stays wave-uniform.  Problems are issued longest
 // first.  A final pass certifies each answer: obj = ½Σ|r_i| and a dual bound
 // −λ·y − ||Zᵀλ||_* for three feasible duals (|λ_i| <= ½: the barrier's λ_i = r_i/(2 s_i),
 // that one with the clearly inactive rows rounded to ±½, and 0); gap = obj − best bound >= 0
@@ -39,9 +40,10 @@ constexpr double kMu0 = 1.0;
 constexpr double kMuEnd = 1e-10;
 constexpr double kKappa = 10.0;
 constexpr double kTolCenter = 1.0;  // λ below which μ decreases
-constexpr double kTolFinal = 1e-6;  // λ at μ_end that ends the solve
+constexpr double kTolFinal = 1e-9;  // λ at μ_end that ends the solve (an error ~λ in x along a flat face)
 constexpr int kFinalSteps = 6;      // or this many Newton steps at μ_end
 constexpr double kPivotFloor = 1e-13;
+constexpr double kPivotDead = 1e150;  // the factor's diagonal at a floored pivot: no step along it
 constexpr double kBreakdown = 1e8;  // a Newton decrement no centred step produces
 
 // packed lower triangle, row by row: (i, j), j <= i
@@ -66,10 +68,13 @@ __device__ __forceinline__ void spd_solve(double (&H)[D * (D + 1) / 2], const do
         double s = H[tri(j, j)];
 #pragma unroll
         for (int k = 0; k < j; ++k) s = __builtin_fma(-H[tri(j, k)], H[tri(j, k)], s);
-        s = s > kPivotFloor ? s : kPivotFloor;
-        const double l = sqrt(s);
+        // a pivot under the floor is a direction fp64 no longer resolves (the optimal face's,
+        // once the rows' curvature ~1/μ² dwarfs the ball's): dividing by the floor would turn
+        // rounding noise into a step along the face, so that component of the step is 0
+        const bool dead = !(s > kPivotFloor);
+        const double l = dead ? kPivotDead : sqrt(s);
         H[tri(j, j)] = l;
-        rd[j] = 1.0 / l;
+        rd[j] = dead ? 0.0 : 1.0 / l;
 #pragma unroll
         for (int i = j + 1; i < D; ++i) {
             double v = H[tri(i, j)];

@@ -32,9 +32,10 @@ constexpr double kMu0 = 1.0;
 constexpr double kMuEnd = 1e-10;
 constexpr double kKappa = 10.0;
 constexpr double kTolCenter = 1.0;
-constexpr double kTolFinal = 1e-6;
+constexpr double kTolFinal = 1e-9;
 constexpr int kFinalSteps = 6;
 constexpr double kPivotFloor = 1e-13;
+constexpr double kPivotDead = 1e150;  // the factor's diagonal at a floored pivot (DEAD)
 constexpr double kBreakdown = 1e8;
 constexpr double kKeepRtol = 1e-9;  // the polish's keep bar (ocx_exact_wide.hip)
 constexpr int kSweeps = 11;         // the polish's threshold sweeps (ocx_exact_wide.hip)
@@ -78,8 +79,10 @@ __device__ __forceinline__ double qmax_abs(const double (&v)[Q]) {
 // time (ocx_exact_wide.hip's LDS factorisation), so the factor is that one's, bit for bit,
 // with an eighth of the passes over the trailing matrix.  cl: LDS [8][DP], the panel's factor
 // columns.
+// DEAD (the Newton system): a pivot under the floor takes no step along that direction
+// (ocx_exact_ball.hip, spd_solve); the polish's ridged systems keep the floor.
 constexpr int kPanel = 8;
-template <int Q>
+template <int Q, bool DEAD = false>
 __device__ void big_factor(double* S, double* sc, double* cl, int lane, double (&si)[Q]) {
     constexpr int DP = 64 * Q, LD = DP + 1, NP = kPanel;
 #pragma unroll
@@ -114,8 +117,9 @@ __device__ void big_factor(double* S, double* sc, double* cl, int lane, double (
         for (int u = 0; u < NP; ++u) {
             const int k = k0 + u;
             double s = ocx_readlane(qpick(pc[u], k >> 6), k & 63);
+            const bool dead = DEAD && !(s > kPivotFloor);
             s = s > kPivotFloor ? s : kPivotFloor;
-            const double l = sqrt(s), rd = 1.0 / l;
+            const double l = dead ? kPivotDead : sqrt(s), rd = dead ? 0.0 : 1.0 / l;
 #pragma unroll
             for (int q = 0; q < Q; ++q) {
                 const int i = lane + 64 * q;
@@ -422,7 +426,7 @@ __global__ __launch_bounds__(64) void ocx_exact_big_kernel(
                 }
             lds_sync();  // the system is complete
             double si[Q], sol[Q], dx[Q];
-            big_factor<Q>(S, sc, cl, lane, si);
+            big_factor<Q, true>(S, sc, cl, lane, si);
             big_solve<Q>(S, lane, si, rhs_g, sol);
 #pragma unroll
             for (int q = 0; q < Q; ++q) dx[q] = cj[q] ? -sol[q] : 0.0;
@@ -921,9 +925,10 @@ __global__ __launch_bounds__(64) void ocx_exact_big_polish_kernel(
             }
             if (best <= 1e-14 * (1.0 + pbest) && bestx <= kKeepRtol * (1.0 + fabs(P0x))) break;
         }
-        if (bestx < g0 && bestx <= kKeepRtol * (1.0 + fabs(P0x))) {
-            // x certifies on its own: keep it (and its step loss), report its objective and gap
-            if (lane == 0) {
+        if (fmin(bestx, g0) <= kKeepRtol * (1.0 + fabs(P0x))) {
+            // x certifies on its own, by the barrier's dual or a rebuilt one: keep it (and its
+            // step loss), and report the better of the two gaps
+            if (bestx < g0 && lane == 0) {
                 obj[o] = P0x;
                 gap[o] = bestx;
             }
@@ -959,7 +964,8 @@ hipError_t launch_big_qn(const WideSrc& rs, int64_t B, int64_t NP, double* actio
                          double* gap, double* step_loss, int32_t* info, hipStream_t st) {
     constexpr int DP = 64 * Q, LD = DP + 1;
     const int64_t total = B * NP;
-    // persistent blocks: about what the LDS lets stay resident (81 KB at Q = 4, 42 KB at Q = 2)
+    // persistent blocks: about what the LDS lets stay resident (big_lds_bytes: about 92 KB at
+    // Q = 4, 47 KB at Q = 2)
     const int blocks = (int)std::min<int64_t>(total, Q == 2 ? 512 : 256);
     // per block: the system and (polish) the active rows, or the system and a weight per row
     int64_t sstride = std::max<int64_t>(2 * (int64_t)DP * LD, (int64_t)DP * LD + rs.T);

@@ -27,9 +27,10 @@ constexpr double kMu0 = 1.0;
 constexpr double kMuEnd = 1e-10;
 constexpr double kKappa = 10.0;
 constexpr double kTolCenter = 1.0;
-constexpr double kTolFinal = 1e-6;
+constexpr double kTolFinal = 1e-9;  // an error ~λ in x along a flat face
 constexpr int kFinalSteps = 6;
 constexpr double kPivotFloor = 1e-13;
+constexpr double kPivotDead = 1e150;  // the factor's diagonal at a floored pivot: no step along it
 constexpr double kBreakdown = 1e8;
 constexpr int RC = 64;  // rows per staged chunk
 
@@ -206,9 +207,10 @@ __global__ __launch_bounds__(64) void ocx_exact_wide_kernel(
             for (int j = 0; j <= lane; ++j) M[lane * LD + j] *= sci * sc[j];
         lds_sync();
         for (int k = 0; k < DP; ++k) {
-            double s = M[k * LD + k];
-            s = s > kPivotFloor ? s : kPivotFloor;
-            const double l = sqrt(s), rd = 1.0 / l;
+            // a pivot under the floor: no step along that direction (ocx_exact_ball.hip, spd_solve)
+            const double s = M[k * LD + k];
+            const bool dead = !(s > kPivotFloor);
+            const double l = dead ? kPivotDead : sqrt(s), rd = dead ? 0.0 : 1.0 / l;
             double lik = 0.0;
             if (lane > k && lane < DP) lik = M[lane * LD + k] * rd;
             lds_sync();  // every lane has read row k's diagonal before lane k rewrites it
@@ -709,9 +711,10 @@ __global__ __launch_bounds__(64) void ocx_exact_polish_kernel(
         }
         if (best <= 1e-14 * (1.0 + pbest) && bestx <= kKeepRtol * (1.0 + fabs(P0x))) break;
     }
-    if (bestx < g0 && bestx <= kKeepRtol * (1.0 + fabs(P0x))) {
-        // x certifies on its own: keep it (and its step loss), report its objective and gap
-        if (lane == 0) {
+    if (fmin(bestx, g0) <= kKeepRtol * (1.0 + fabs(P0x))) {
+        // x certifies on its own, by the barrier's dual or a rebuilt one: keep it (and its step
+        // loss), and report the better of the two gaps
+        if (bestx < g0 && lane == 0) {
             obj[o] = P0x;
             gap[o] = bestx;
         }

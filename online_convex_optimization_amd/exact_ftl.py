@@ -21,7 +21,8 @@ minimiser maximises x·S_t over the ball (engine.ftl_prefix_actions_batch / ftl_
   cvxpy picks) approaches the face's analytic centre.  So tied prefixes leave the closed
   form (ocx_exact_poly_tie / the oracle's _poly_tie): for l1 two or more coordinates at the
   largest |S_j| > 0, for linf a zero coordinate of S_t that a row of the prefix touched.
-  The general solver below answers those sequences (the analytic centre); for linf that
+  The general solver below answers those sequences (the analytic centre, to within 7e-6 on
+  the tied faces tested, most to 1e-6); for linf that
   sends the flip / switching families, whose rows touch one coordinate at a time, to the
   O(T^2) general path.  S_t = 0 (e.g. the empty prefix) keeps x = 0, which is that centre.
   Which point of the face cvxpy itself returns is solver-dependent: parity unpinned.

@@ -159,7 +159,8 @@ def _poly_tie(theta: np.ndarray, touched: np.ndarray, norm: str) -> bool:
     """Prefixes whose LP optimum is a face the closed form does not centre (kernels:
     ocx_exact_poly_tie): l1 with two or more coordinates at max |S_j| > 0; linf with S_j = 0
     in a coordinate some row of the prefix touched.  The engine answers those sequences with
-    the general solver (the analytic centre of the face, as interior-point cvxpy backends)."""
+    the general solver (the analytic centre of the face to about 1e-6, as interior-point cvxpy
+    backends)."""
     if norm == "l1":
         a = np.abs(theta)
         m = float(a.max(initial=0.0))

@@ -310,7 +310,7 @@ def test_tied_prefixes_take_the_general_solvers_centre(eng, norm):
     touched by rows of both signs returns to S_j = 0 (linf).  The closed form would play the
     first coordinate / 0 there; such sequences now leave the closed form's regime and the
     engine answers with the general solver — the analytic centre of the optimal face, the
-    interior-point limit — so the batched closed-form path and the general solver give the
+    interior-point limit (how closely: test_gpu_exact_centre.py) — so the batched closed-form path and the general solver give the
     same actions, at the LP optimum."""
     T, d = 24, 5
     z = np.zeros((2, T, d))
