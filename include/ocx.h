@@ -62,7 +62,9 @@
  * ocx_simulate_alg_etas_batch) and the threshold sweep symbols (ocx_smart_thresholds_group,
  * ocx_dev_simulate_smart_thresholds, ocx_simulate_smart_thresholds_batch), and for the SMART
  * regret-curve symbols (ocx_smart_curve_group, ocx_dev_simulate_smart_curve,
- * ocx_simulate_smart_curve_batch).
+ * ocx_simulate_smart_curve_batch), and for the FTRL-vs-exact-FTL regret-curve symbols
+ * (ocx_ftrl_exact_curve_workspace_bytes, ocx_dev_ftrl_vs_exact_curve,
+ * ocx_ftrl_vs_exact_curve_batch).
  *
  * Checking the ABI: one intermediate 0.1.x tree exported ocx_ftrl_vs_exact_batch WITH a
  * `norm` argument under the same symbol and the same version number as the release without
@@ -463,6 +465,51 @@ int ocx_dev_ftrl_vs_exact_ex(const ocx_layout* L, const double* z_tiled, const d
                              double eta0, double* cum_ftrl, double* cum_exact, double* comp_exact,
                              double* comp_ftl, double* cmp_action, int32_t* regime, int norm,
                              int flags, void* stream);
+
+/* FTRL-vs-exact-FTL regret curves: exact_ftl_driver.py:157-190 observed at K checkpoint
+ * horizons in one pass.  Both loops of ocx_dev_ftrl_vs_exact_ex are online, so for checkpoints
+ * 0 <= t_1 < ... < t_K <= T (strictly increasing; 0 and T allowed) column k of every output,
+ *   cum_ftrl[b][k], cum_exact[b][k], comp_exact[b][k], comp_ftl[b][k], regime[b][k],
+ *   cmp_action[b][k][:],
+ * carries the bits ocx_dev_ftrl_vs_exact_ex gives on the batch truncated at t_k, with the same
+ * layout (which does not depend on T), norm and flags; t_k = 0 gives zero losses.
+ *
+ * bytes of caller-owned device workspace for K checkpoints in layout L (with_comp_ftl: the call
+ * will pass a comp_ftl output); 0 for K == 0 or an empty batch; negative ocx_status on error
+ * (bad layout, K < 0, K > T + 1) */
+int64_t ocx_ftrl_exact_curve_workspace_bytes(const ocx_layout* L, int64_t K, int with_comp_ftl);
+
+/* device: checkpoints is a DEVICE int64 array [K], strictly increasing in [0, L->T] — a
+ * precondition the call cannot see: an array that breaks it gives meaningless numbers, but the
+ * kernels never leave the batch, the outputs and the workspace whatever it holds;
+ * cum_ftrl / cum_exact / comp_exact: device [B][K] row-major, required; comp_ftl [B][K]
+ * nullable; cmp_action [B][K][d] nullable; regime [B][K] int32, required; closed [B][K] int32
+ * nullable (1 = both comparator losses in closed form);
+ * norm, flags: as in ocx_dev_ftrl_vs_exact_ex (OCX_ALG_CLOSED_COMPARATOR / OCX_ALG_CLIPPED_ROWS,
+ * OCX_ALG_TREE_SUMS).  The closed form is per (sequence, checkpoint): a pair the kernel cannot
+ * certify — every pair with flags 0, every l1 / linf pair — gets the streamed pass over its
+ * prefix, and a certified sequence keeps the closed form whatever shares its wave;
+ * workspace: workspace_bytes >= ocx_ftrl_exact_curve_workspace_bytes(L, K, comp_ftl != NULL) of
+ * device memory, 8-byte aligned, the call's own until the stream has passed it;
+ * K == 0 and B == 0 launch nothing; T == 0 is valid;
+ * asynchronous, no allocation, no sync: capture-safe like the other dev entry points.
+ * Cost: one read of z when every pair takes the closed form; otherwise the prefixes of the
+ * other pairs are read once more (at most sum_k t_k rows per sequence). */
+int ocx_dev_ftrl_vs_exact_curve(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                                double eta0, const int64_t* checkpoints, int64_t K,
+                                double* cum_ftrl, double* cum_exact, double* comp_exact,
+                                double* comp_ftl, double* cmp_action, int32_t* regime,
+                                int32_t* closed, int norm, int flags, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
+/* host: numpy buffers in, [B][K] out (cmp_action [B][K][d]); checkpoints is a HOST array,
+ * validated here (order, range, K >= 0) before any device is touched.  lanes_per_seq chooses the
+ * closed form and the butterfly sums as ocx_ftrl_vs_exact_batch_ex does. */
+int ocx_ftrl_vs_exact_curve_batch(const double* z, const double* y, int64_t B, int64_t T,
+                                  int64_t d, double eta0, const int64_t* checkpoints, int64_t K,
+                                  double* cum_ftrl, double* cum_exact, double* comp_exact,
+                                  double* comp_ftl, double* cmp_action, int32_t* regime,
+                                  int32_t* closed, int norm, int lanes_per_seq, int device);
 
 /* fast_algorithms.py:118-164 on device; thresh [B] device. */
 int ocx_dev_simulate_smart(const ocx_layout* L, const double* z_tiled, const double* y_tiled,

@@ -42,6 +42,7 @@
 // the comparator pass clamps its horizon to [0, T].
 #include "ocx_alg_pipe.h"
 #include "ocx_alg_step.h"
+#include "ocx_curve_ck.h"
 #include "ocx_device_math.h"
 #include "ocx_dispatch.h"
 #include "ocx_internal.h"
@@ -59,29 +60,10 @@ struct CurveArgs {
     int* ws_need;
 };
 
-// The checkpoint list is read-only for the kernels' lifetime and indexed wave-uniformly: read
-// through the constant address space it is a scalar load, which waits on the scalar counter
-// alone.  (As a global load it compiled to a vector load followed by a wait for EVERY
-// outstanding vector access — the emission's stores and the ring's look-ahead rows.  Measured,
-// the drain was not what an emission costs: DESIGN.md §3.9.)
-typedef const int64_t __attribute__((address_space(4))) * curve_ck_ptr;
-__device__ __forceinline__ int64_t curve_ck(const int64_t* ck, int64_t k) {
-    return ((curve_ck_ptr)ck)[k];
-}
-
-// checkpoint k as the loop's step type, wave-uniform: values past the horizon become T + 1
-// (never met inside the loop; emitted after it), negative ones 0; none left: T + 1
+// checkpoint k as the loop's step type (curve_ck / curve_next: ocx_curve_ck.h)
 template <class IT>
 __device__ __forceinline__ IT curve_next(const CurveArgs& a, int64_t k) {
-    const int64_t T = a.p.T;
-    int64_t v = T + 1;
-    if (k < a.K) {
-        v = curve_ck(a.ck, k);
-        v = v < 0 ? 0 : (v > T ? T + 1 : v);
-    }
-    const int lo = __builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)v);
-    const int hi = __builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
-    return (IT)(int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
+    return ::curve_next<IT>(a.ck, a.K, a.p.T, k);
 }
 
 // Emission of checkpoint k at horizon tk, th = θ_{tk}.  Whole wave active (lane exchanges).

@@ -17,57 +17,9 @@
 // exact-FTL sums (‖θ_e‖², ‖z‖²) run as one 4-way chain; then z·x_e.
 #include "ocx_device_math.h"
 #include "ocx_dispatch.h"
+#include "ocx_ftrl_exact_step.h"
 #include "ocx_internal.h"
 #include "ocx_sim_kernels.h"
-
-// N per-sequence totals at once; prod(j, k) is product k of this lane's coordinate j.
-// Each total keeps the reference's order (sequential over j, then lane to lane in
-// chain mode; lane-local then the butterfly in tree mode).
-template <int C, int P, bool CHAIN, int N, class F>
-__device__ __forceinline__ void ocx_totals(F&& prod, double (&out)[N], int lane) {
-    double acc[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) acc[k] = 0.0;
-    if constexpr (!CHAIN || P == 1) {
-#pragma unroll
-        for (int j = 0; j < C; ++j)
-#pragma unroll
-            for (int k = 0; k < N; ++k) acc[k] += prod(j, k);
-#pragma unroll
-        for (int k = 0; k < N; ++k) out[k] = ocx_seq_sum<P>(acc[k]);
-    } else if constexpr (P < OCX_CHAIN_WIDE_P) {
-        const int c = lane % P;
-        for (int cc = 0; cc < P; ++cc) {
-            if (c == cc) {
-#pragma unroll
-                for (int j = 0; j < C; ++j)
-#pragma unroll
-                    for (int k = 0; k < N; ++k) acc[k] += prod(j, k);
-            }
-            if (cc + 1 < P) {
-#pragma unroll
-                for (int k = 0; k < N; ++k) acc[k] = ocx_dpp<0x138>(acc[k]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < N; ++k) out[k] = __shfl(acc[k], lane - c + P - 1, 64);
-    } else {
-        // diagonal chain (ocx_device_math.h): every lane adds, the last lane's is the total
-#pragma unroll ocx_chain_unroll(P, C)
-        for (int cc = 0; cc < P; ++cc) {
-#pragma unroll
-            for (int j = 0; j < C; ++j)
-#pragma unroll
-                for (int k = 0; k < N; ++k) acc[k] += prod(j, k);
-            if (cc + 1 < P) {
-#pragma unroll
-                for (int k = 0; k < N; ++k) acc[k] = ocx_dpp<0x138>(acc[k]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < N; ++k) out[k] = ocx_bcast_last<P>(acc[k], lane);
-    }
-}
 
 template <int C, int P, bool CHAIN, int NB>
 __global__ __launch_bounds__(OCX_BLOCK) void ocx_ftrl_exact_kernel(

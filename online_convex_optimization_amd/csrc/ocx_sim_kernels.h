@@ -217,6 +217,17 @@ hipError_t ocx_launch_ftrl_exact(const ocx_layout* L, const double* zt, const do
                                  double eta0, double* cum_r, double* cum_e, double* comp_e,
                                  double* comp_f, double* cmp_out, int* regime, hipStream_t st,
                                  int onepass = 0, int norm = 0);
+// Its curve form (ocx_ftrl_exact_curve.hip): both loops observed at the K checkpoints ck (device,
+// strictly increasing in [0, T]) in one pass; cum_r / cum_e / comp_e / regime [B][K], comp_f and
+// closed_out [B][K] nullable, cmp_out [B][K][d] nullable.  Then the streamed comparator of the
+// pairs the closed form did not take, from ws (ocx_ftrl_exact_curve_ws_bytes bytes of device
+// memory; with_comp_f: comp_f != nullptr).
+int64_t ocx_ftrl_exact_curve_ws_bytes(const ocx_layout* L, int64_t K, int with_comp_f);
+hipError_t ocx_launch_ftrl_exact_curve(const ocx_layout* L, const double* zt, const double* yt,
+                                       double eta0, const int64_t* ck, int64_t K, double* cum_r,
+                                       double* cum_e, double* comp_e, double* comp_f,
+                                       double* cmp_out, int* regime, int* closed_out, int onepass,
+                                       int norm, void* ws, hipStream_t st);
 // float32 twin (algorithms.py, ocx_twin32.hip): P = 1 layouts, d <= 32
 // algo 0 FTRL, 1 FTL, 2 SMART (thresh[B]); clip: rows are raw g(T) normals to round to
 // float and clip in float32 (algorithms.py:157-160)

@@ -235,6 +235,39 @@ def _exact_pair(db, B, d, torch, norm: str = "l2") -> Dict[str, np.ndarray]:
     return {"FTRL": ftrl[:B].cpu().numpy(), "FTL (exact)": ftl[:B].cpu().numpy()}
 
 
+def exact_case_regret_curves(title: str, T_grid: Sequence[int], *, runs: int, replicates: int,
+                             base_seed: int = 0, d: int = 5, p: float = 0.10,
+                             block_len: int = 20, lanes_per_seq: int = 1, device: int = 0,
+                             norm: str = "l2") -> Dict[str, np.ndarray]:
+    """Both regrets of exact_case_regrets against the horizon, from ONE batch: the case's
+    sequences are generated once at horizon max(T_grid) and the curve
+    (DeviceBatch.ftrl_vs_exact_curve_general) is read at every T of ``T_grid`` (strictly
+    increasing) in one pass.  Returns {"FTRL", "FTL (exact)"}, each [runs * replicates, K];
+    column k is the regret on the first T_k rows of that batch.
+
+    What the columns are depends on the family.  For the deterministic families (label flips,
+    switching leaders) the prefix of the long sequence IS the reference's sequence at each T,
+    so column k holds the reference's numbers: exact_case_regrets(title, T_k), bit for bit.
+    For the random families (i.i.d., Massart) the reference draws a fresh sequence per T
+    (sequence_generation.py:61-62: the generator is seeded with T), so the curve is the
+    anytime regret on the longest horizon's rows — a different sample of the same
+    distribution, not the reference's per-T numbers.  exact_evaluate_stream_with_stats
+    therefore keeps one batch per T."""
+    family, stream0 = CASE_FAMILIES[title]
+    grid = np.asarray(T_grid)
+    ck = engine._checkpoints(grid, int(grid.max()) if grid.size else 0)  # ValueError if bad
+    B, K = runs * replicates, int(ck.size)
+    if B == 0 or K == 0:
+        return {k: np.zeros((B, K)) for k in EXACT_ALGOS}
+    db = engine.DeviceBatch(B, int(ck[-1]), d, lanes_per_seq=lanes_per_seq, device=device)
+    run_idx = np.repeat(np.arange(runs), replicates)
+    rep_idx = np.tile(np.arange(replicates), runs)
+    db.generate_family(family, base_seed + 2025 * (run_idx + 1), stream0 + rep_idx, p=p,
+                       block_len=block_len)
+    out = db.ftrl_vs_exact_curve_general(ck, SQRT2, norm=norm)
+    return {"FTRL": out["ftrl"][:B].cpu().numpy(), "FTL (exact)": out["exact"][:B].cpu().numpy()}
+
+
 def exact_evaluate_stream_with_stats(title: str, T_grid: Sequence[int], *, runs: int,
                                      replicates: int, base_seed: int = 0, device: int = 0,
                                      norm: str = "l2") -> Stats:

@@ -479,6 +479,65 @@ def ftrl_vs_exact_batch(z, y, eta0: float = SQRT2, *, norm: str = "l2",
     return out
 
 
+def _general_curve_columns(step_loss, obj, ck: np.ndarray):
+    """The general solver's columns of an exact curve from its all-prefix results (step_loss,
+    obj [n, Tm + 1]): exact FTL's cumulative loss in step order at every horizon of ``ck``
+    (cumsum(step_loss)[t_k - 1], 0 at t_k = 0) and the comparator loss obj[:, t_k]."""
+    n = step_loss.shape[0]
+    run = np.concatenate([np.zeros((n, 1)), np.cumsum(step_loss[:, :-1], axis=1)], axis=1)
+    return run[:, ck], obj[:, ck]
+
+
+def ftrl_vs_exact_curve_batch(z, y, checkpoints, eta0: float = SQRT2, *, norm: str = "l2",
+                              lanes_per_seq: int = LANES_BEST, device: int = 0,
+                              check_regime: bool = True, with_ftl_comparator: bool = False):
+    """FTRL-vs-exact-FTL regret curves (exact_ftl_driver.py:157-190 against the horizon) for B
+    sequences in one pass (ocx_ftrl_vs_exact_curve_batch): ftrl_vs_exact_batch observed at
+    every horizon of ``checkpoints`` (strictly increasing in [0, T]).
+
+    Returns a dict of [B, K] arrays ``ftrl``, ``exact``, ``cum_ftrl``, ``cum_exact``, ``comp``,
+    ``in_regime`` (bool), ``closed`` (int32), ``action`` [B, K, d], ``exact_gap_max`` and, with
+    ``with_ftl_comparator``, ``comp_ftl``; column k is ftrl_vs_exact_batch on (z[:, :t_k],
+    y[:, :t_k]) with the same arguments.  With ``check_regime`` the pairs outside the closed
+    form's regime are filled by ONE general solve (exact_ball_solve over all prefixes up to the
+    largest checkpoint) of the sequences that have such a pair; the other pairs keep the
+    closed form."""
+    code = _norm_code(norm)
+    z = _f64(z)
+    y = _f64(y)
+    B, T, d = _check_zy(z, y)
+    ck = _checkpoints(checkpoints, T)
+    K = int(ck.size)
+    cr, ce, cmp_e, cmp_f = (np.zeros((B, K)) for _ in range(4))
+    act = np.zeros((B, K, d))
+    rg = np.zeros((B, K), dtype=np.int32)
+    closed = np.zeros((B, K), dtype=np.int32)
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    _lib.call("ocx_ftrl_vs_exact_curve_batch", ptr(z), ptr(y), B, T, d, float(eta0),
+              ck.ctypes.data_as(_lib.c_i64p), K, ptr(cr), ptr(ce), ptr(cmp_e),
+              ptr(cmp_f) if with_ftl_comparator else None, ptr(act), rg.ctypes.data_as(i32p),
+              closed.ctypes.data_as(i32p), code, int(lanes_per_seq), int(device))
+    ok = rg.astype(bool)
+    worst = 0.0
+    bad = np.flatnonzero((~ok).any(axis=1)) if K else np.zeros(0, dtype=np.int64)
+    if check_regime and bad.size:
+        Tm = int(ck[-1])
+        res = exact_ball_solve(z[bad, :Tm], y[bad, :Tm], norm=norm, all_prefixes=True,
+                               device=device)
+        worst = check_certificates(res["obj"], res["gap"], res["info"])
+        gcum, gcomp = _general_curve_columns(res["step_loss"], res["obj"], ck)
+        m = ~ok[bad]                                   # only these pairs change
+        ce[bad] = np.where(m, gcum, ce[bad])
+        cmp_e[bad] = np.where(m, gcomp, cmp_e[bad])
+        act[bad] = np.where(m[:, :, None], res["actions"][:, ck], act[bad])
+    out = {"ftrl": cr - cmp_e, "exact": ce - cmp_e, "cum_ftrl": cr, "cum_exact": ce,
+           "comp": cmp_e, "action": act, "in_regime": ok, "closed": closed,
+           "exact_gap_max": worst}
+    if with_ftl_comparator:
+        out["comp_ftl"] = cmp_f
+    return out
+
+
 def gT_regrets(T: int, runs: int, *, base_seed: int = 0, d: int = 5, eta0: float = SQRT2,
                run0: int = 0, lanes_per_seq: int = LANES_BEST, device: int = 0) -> np.ndarray:
     """Regrets of FTRL on _rng(base_seed, T, run) sequences, run in [run0, run0+runs),
@@ -1082,6 +1141,122 @@ class DeviceBatch:
             self.cum_exact[bad] = torch.as_tensor(gcum).to(self.device)
             self.comp[bad] = res["obj"][:, T]
         return regime
+
+    def ftrl_vs_exact_curve(self, checkpoints, eta0: float = SQRT2, *, norm: str = "l2",
+                            closed_comparator: Optional[bool] = None,
+                            with_ftl_comparator: bool = False, with_actions: bool = False):
+        """FTRL-vs-exact-FTL regret curves of the resident batch (ocx_dev_ftrl_vs_exact_curve,
+        async): both loops of ftrl_vs_exact observed at every horizon of ``checkpoints``
+        (strictly increasing in [0, T], validated here) in one pass over z.  Returns a dict of
+        [B, K] device tensors: ``ftrl`` and ``exact`` (regrets against the prefix's exact
+        comparator), ``cum_ftrl``, ``cum_exact``, ``comp``, ``in_regime`` and ``closed`` (int32;
+        closed: both comparator losses in closed form); with ``with_ftl_comparator`` also
+        ``comp_ftl``, with ``with_actions`` ``action`` [B, K, d].  Column k is what
+        ftrl_vs_exact gives on the batch truncated at t_k, bit for bit in the same layout;
+        ``closed_comparator`` and the butterfly sums default as there.  A pair outside the
+        regime (``in_regime`` 0) keeps the closed form's numbers, as ftrl_vs_exact does:
+        ftrl_vs_exact_curve_general fills those."""
+        torch = self.torch
+        code = _norm_code(norm)
+        ck = _checkpoints(checkpoints, self.L.T)
+        K, B, d = int(ck.size), int(self.L.B), int(self.L.d)
+        if closed_comparator is None:
+            closed_comparator = not self.exact
+        flags = _lib.OCX_ALG_CLOSED_COMPARATOR if closed_comparator else 0
+        if self.best and self.L.chain:
+            flags |= _lib.OCX_ALG_TREE_SUMS  # as ftrl_vs_exact
+        nbytes = int(_lib.load().ocx_ftrl_exact_curve_workspace_bytes(
+            self._lp(), K, int(bool(with_ftl_comparator))))
+        if nbytes < 0:
+            _lib.check(nbytes, "ocx_ftrl_exact_curve_workspace_bytes")
+        with torch.cuda.device(self.device), self._on_stream():
+            ckd = torch.as_tensor(ck).to(self.device)
+            out = {k: torch.zeros((B, K), dtype=torch.float64, device=self.device)
+                   for k in ("cum_ftrl", "cum_exact", "comp")}
+            if with_ftl_comparator:
+                out["comp_ftl"] = torch.zeros((B, K), dtype=torch.float64, device=self.device)
+            if with_actions:
+                out["action"] = torch.zeros((B, K, d), dtype=torch.float64, device=self.device)
+            for k in ("in_regime", "closed"):
+                out[k] = torch.zeros((B, K), dtype=torch.int32, device=self.device)
+            ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self.device)
+        if K and B:
+            self._call("ocx_dev_ftrl_vs_exact_curve", self._lp(), self.z.data_ptr(),
+                       self.y.data_ptr(), float(eta0), ckd.data_ptr(), K,
+                       out["cum_ftrl"].data_ptr(), out["cum_exact"].data_ptr(),
+                       out["comp"].data_ptr(),
+                       out["comp_ftl"].data_ptr() if with_ftl_comparator else None,
+                       out["action"].data_ptr() if with_actions else None,
+                       out["in_regime"].data_ptr(), out["closed"].data_ptr(), code, flags,
+                       ws.data_ptr(), ws.numel() * 8, self._sp)
+        with self._on_stream():
+            out["ftrl"] = out["cum_ftrl"] - out["comp"]
+            out["exact"] = out["cum_exact"] - out["comp"]
+        self._keep_exact_curve = self._hold(ckd, ws)
+        return out
+
+    def ftrl_vs_exact_curve_general(self, checkpoints, eta0: float = SQRT2, *, norm: str = "l2",
+                                    closed_comparator: Optional[bool] = None,
+                                    with_ftl_comparator: bool = False,
+                                    with_actions: bool = False):
+        """ftrl_vs_exact_curve with every pair's exact side valid: the pairs with
+        ``in_regime`` 0 get the general solver's numbers — ONE exact_ball_solve-style call over
+        all prefixes up to the largest checkpoint, for the sequences with any such pair:
+        cum_exact[b, k] = cumsum(step_loss)[t_k - 1] (0 at t_k = 0), comp[b, k] = obj[b, t_k],
+        action = actions[b, t_k]; a prefix still in the regime keeps its closed form, as a
+        truncated call would.  Certificates are checked (check_certificates; the worst gap is
+        left in self.exact_gap_max).  Synchronises once."""
+        torch = self.torch
+        out = self.ftrl_vs_exact_curve(checkpoints, eta0, norm=norm,
+                                       closed_comparator=closed_comparator,
+                                       with_ftl_comparator=with_ftl_comparator,
+                                       with_actions=with_actions)
+        ck = _checkpoints(checkpoints, self.L.T)
+        K, d = int(ck.size), int(self.L.d)
+        self.exact_gap_max = 0.0
+        if K == 0 or self.L.B == 0:
+            return out
+        with self._on_stream():
+            out_of = out["in_regime"] == 0                  # [B, K]
+            if not bool(out_of.any().item()):
+                return out
+            bad = torch.nonzero(out_of.any(dim=1)).flatten()
+            nb, Tm = int(bad.numel()), int(ck[-1])
+            zb, yb = self.rows_of(bad)
+            zb, yb = zb[:, :Tm].contiguous(), yb[:, :Tm].contiguous()
+            res = {"actions": torch.zeros((nb, Tm + 1, d), dtype=torch.float64,
+                                          device=self.device)}
+            for k in ("obj", "gap", "step_loss"):
+                res[k] = torch.zeros((nb, Tm + 1), dtype=torch.float64, device=self.device)
+            res["info"] = torch.zeros((nb, Tm + 1), dtype=torch.int32, device=self.device)
+            self._call("ocx_dev_exact_ball_solve", zb.data_ptr(), yb.data_ptr(), nb, Tm, d,
+                       _norm_code(norm), 1, res["actions"].data_ptr(), res["obj"].data_ptr(),
+                       res["gap"].data_ptr(), res["step_loss"].data_ptr(),
+                       res["info"].data_ptr(), self._sp)
+            self._hold(zb, yb)
+            host = {k: res[k].cpu().numpy() for k in ("obj", "gap", "info", "step_loss")}
+            self.exact_gap_max = check_certificates(host["obj"], host["gap"], host["info"])
+            gcum, gcomp = _general_curve_columns(host["step_loss"], host["obj"], ck)
+            m = out_of[bad]                                 # [nb, K]: only these pairs change
+            ckd = torch.as_tensor(ck).to(self.device)
+            new_cum = torch.as_tensor(gcum).to(self.device)
+            new_comp = torch.as_tensor(gcomp).to(self.device)
+            out["cum_exact"][bad] = torch.where(m, new_cum, out["cum_exact"][bad])
+            out["comp"][bad] = torch.where(m, new_comp, out["comp"][bad])
+            if with_actions:
+                acts = res["actions"][:, ckd, :]            # [nb, K, d]
+                out["action"][bad] = torch.where(m[:, :, None], acts, out["action"][bad])
+            out["ftrl"] = out["cum_ftrl"] - out["comp"]
+            out["exact"] = out["cum_exact"] - out["comp"]
+        return out
+
+    def exact_comparison_curves(self, checkpoints, eta0: float = SQRT2, norm: str = "l2"):
+        """The two lines of the reference's exact comparison figure (exact_ftl_driver.py:
+        157-190) against the horizon, from this resident batch: ``FTRL`` and ``FTL (exact)``,
+        each a [B, K] device tensor — the regrets of ftrl_vs_exact_curve, the counterpart of
+        comparison_curves.  Column k is the regret on the batch truncated at t_k."""
+        out = self.ftrl_vs_exact_curve(checkpoints, eta0, norm=norm)
+        return {"FTRL": out["ftrl"], "FTL (exact)": out["exact"]}
 
     def rows_of(self, seqs):
         """z [n, T, d] and y [n, T] (device, row-major, contiguous) of the sequences ``seqs``
