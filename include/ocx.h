@@ -64,7 +64,8 @@
  * regret-curve symbols (ocx_smart_curve_group, ocx_dev_simulate_smart_curve,
  * ocx_simulate_smart_curve_batch), and for the FTRL-vs-exact-FTL regret-curve symbols
  * (ocx_ftrl_exact_curve_workspace_bytes, ocx_dev_ftrl_vs_exact_curve,
- * ocx_ftrl_vs_exact_curve_batch).
+ * ocx_ftrl_vs_exact_curve_batch), and for the float32 twin's column symbols
+ * (ocx_twin32_cols_group, ocx_dev_twin32_cols, ocx_twin32_cols_batch).
  *
  * Checking the ABI: one intermediate 0.1.x tree exported ocx_ftrl_vs_exact_batch WITH a
  * `norm` argument under the same symbol and the same version number as the release without
@@ -293,6 +294,43 @@ int ocx_twin32_batch(const float* z, const float* y, int64_t B, int64_t T, int64
 int ocx_dev_twin32(const ocx_layout* L, const double* z_tiled, const double* y_tiled, int algo,
                    double eta0, const double* thresh, float* result, double* cum_loss,
                    float* comp_loss, int64_t* switch_step, void* stream);
+/* Twin sweeps: the float32 twin for K columns (horizon t_k, algorithm, threshold) per staging
+ * of a sequence's rows and per prefix re-scan (one wavefront per sequence).
+ * Column k carries the bits of ocx_dev_twin32(algos[k], eta0, thresh[:, k]) on a batch made of
+ * the first horizons[k] rows:
+ *   result[b][k] float32, cum_loss[b][k] double, comp_loss[b][k] float32, switch_step[b][k]
+ *   int64 (-1: never switched, and every FTRL / FTL column).
+ * horizons [K]: non-decreasing in [0, T], duplicates legal (FTRL, FTL, SMART and EMP at the
+ * same t_k); a horizon of 0 gives 0.0f, 0.0, 0.0f, -1.  algos [K]: 0 FTRL, 1 FTL, 2 SMART.
+ * eta0: one scalar per call.  SMART's pre-switch prefix loss at step t is the comparator loss
+ * of a run truncated at t + 1 and FTL is the SMART column that never switches, so one re-scan
+ * per step decides every column; a launch serves a group of consecutive columns and stops at
+ * the group's last horizon.  The rows of the call's last horizon must fit the LDS,
+ * t_K * (C + 1) * 4 <= 60 KiB (C = d rounded up to even: 2194 rows at d = 5); otherwise
+ * OCX_E_UNSUPPORTED before anything is launched (no lane-per-sequence form, no clip variant).
+ *
+ * columns one launch serves in layout L (the smallest of 1, 2, 4, 8 that holds K, at most
+ * 8 for d <= 8, 4 for d <= 16, 2 for d <= 32; negative ocx_status on error) */
+int ocx_twin32_cols_group(const ocx_layout* L, int64_t K);
+/* device: one-lane layout (lanes_per_seq = -1), as ocx_dev_twin32.  horizons and algos are
+ * HOST arrays [K], read and validated at call time (they travel in the kernel arguments): a
+ * bad list (order, range, algorithm, a SMART column with thresh == NULL) returns
+ * OCX_E_INVALID and nothing is launched.  thresh: DEVICE [B][K] row-major, read for SMART
+ * columns only, NULL allowed when no column is SMART.  result [B][K] device; cum_loss,
+ * comp_loss, switch_step [B][K] device, each nullable.  K == 0, B == 0 and T == 0 are valid.
+ * Asynchronous, no allocation, no copy, no sync: capture-safe like the other dev entry points
+ * (a captured graph keeps the lists it was captured with). */
+int ocx_dev_twin32_cols(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                        int64_t K, const int64_t* horizons, const int32_t* algos, double eta0,
+                        const double* thresh, float* result, double* cum_loss, float* comp_loss,
+                        int64_t* switch_step, void* stream);
+/* host: float32 z [B][T][d], y [B][T] in, [B][K] out (thresh HOST [B][K], nullable when no
+ * column is SMART; the last three outputs nullable), on the library's cached buffers like
+ * ocx_twin32_batch; the lists are validated before any device is touched. */
+int ocx_twin32_cols_batch(const float* z, const float* y, int64_t B, int64_t T, int64_t d,
+                          int64_t K, const int64_t* horizons, const int32_t* algos, double eta0,
+                          const double* thresh, float* result, double* cum_loss, float* comp_loss,
+                          int64_t* switch_step, int device);
 /* The float32 twin's g(T) inner loop (algorithms.py:150-169): the regrets of runs
  * run0 .. run0+R-1 of _rng(base_seed, T, run), rows rounded to float32 and clipped in
  * float32, FTRL with eta0; on device (generator + twin kernel), nothing but the regrets

@@ -107,6 +107,15 @@ int ocx_test_simulate_smart_wave_cols(const ocx_layout* L, const double* z_tiled
                                       double* regret, int64_t* switch_step,
                                       unsigned long long* stats, int group, void* stream);
 
+/* ocx_dev_twin32_cols in launches of `group` (1, 2, 4 or 8) consecutive columns instead of
+ * ocx_twin32_cols_group's choice, so a test reaches every instantiated width.
+ * OCX_E_UNSUPPORTED where group * C > 64 (group 8 above 8 coordinates, group 4 above 16).
+ * Asynchronous like the product call. */
+int ocx_test_twin32_cols(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                         int64_t K, const int64_t* horizons, const int32_t* algos, double eta0,
+                         const double* thresh, float* result, double* cum_loss, float* comp_loss,
+                         int64_t* switch_step, int group, void* stream);
+
 /* Batches that have entered the trailing pipeline (ocx_run_gen_sim_trailing) in this process
  * so far: lets a test assert that a call took that path rather than the sequential loop. */
 int64_t ocx_test_trailing_batches(void);

@@ -23,6 +23,7 @@ c_int = ctypes.c_int
 c_double = ctypes.c_double
 c_vp = ctypes.c_void_p
 c_fp = ctypes.POINTER(ctypes.c_float)
+c_i32p = ctypes.POINTER(ctypes.c_int32)
 
 
 class OCXError(RuntimeError):
@@ -132,6 +133,11 @@ SIGNATURES = {
     "ocx_dev_twin32": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_int, c_double, c_vp, c_vp,
                                c_vp, c_vp, c_vp, c_vp]),
     "ocx_twin32_gT_regrets": (c_int, [c_u64, c_i64, c_i64, c_i64, c_i64, c_double, c_fp, c_int]),
+    "ocx_twin32_cols_group": (c_int, [ctypes.POINTER(Layout), c_i64]),
+    "ocx_dev_twin32_cols": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_i64, c_i64p, c_i32p,
+                                    c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "ocx_twin32_cols_batch": (c_int, [c_fp, c_fp, c_i64, c_i64, c_i64, c_i64, c_i64p, c_i32p,
+                                      c_double, c_dp, c_fp, c_dp, c_fp, c_i64p, c_int]),
     "ocx_exact_ball_solve": (c_int, [c_dp, c_dp, c_i64, c_i64, c_i64, c_int, c_int, c_dp, c_dp,
                                      c_dp, c_dp, ctypes.POINTER(ctypes.c_int32), c_int]),
     "ocx_dev_exact_ball_solve": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_vp,
@@ -161,6 +167,8 @@ TEST_SIGNATURES = {
     "ocx_test_simulate_smart_wave_cols": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_i64p, c_vp,
                                                   c_i64, c_double, c_vp, c_vp, c_vp, c_int,
                                                   c_vp]),
+    "ocx_test_twin32_cols": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_i64, c_i64p, c_i32p,
+                                     c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp]),
     "ocx_test_trailing_batches": (c_i64, []),
 }
 OCX_VERSION = 400  # include/ocx.h OCX_VERSION: the ABI these signatures describe

@@ -2062,6 +2062,144 @@ int ocx_dev_twin32(const ocx_layout* L, const double* z_tiled, const double* y_t
     return OCX_OK;
 }
 
+// ---- float32 twin, K (horizon, algorithm, threshold) columns (ocx_twin32_cols.hip)
+// the smallest instance that holds K columns, capped at the layout's widest
+static int twin32_cols_group_for(const ocx_layout* L, int64_t K) {
+    int g = ocx_twin32_cols_max_group(L);
+    while (g > 1 && g / 2 >= K) g /= 2;
+    return g;
+}
+
+static int twin32_cols_check_layout(const ocx_layout* L) {
+    if (int rc = check_layout(L)) return rc;
+    if (L->P != 1) return fail(OCX_E_INVALID, "the float32 twin needs a one-lane layout (lanes_per_seq = -1)");
+    if (L->d > 32) return fail(OCX_E_UNSUPPORTED, "the float32 twin supports d <= 32");
+    return OCX_OK;
+}
+
+// the host lists of a column call: horizons as check_horizons, algos in 0..2, SMART needs thresh
+static int twin32_cols_check_lists(const int64_t* horizons, const int32_t* algos, int64_t K,
+                                   int64_t T, const void* thresh, int64_t B) {
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    if (int rc = check_horizons(horizons, K, T)) return rc;
+    if (K > 0 && !algos) return fail(OCX_E_INVALID, "NULL algos");
+    for (int64_t k = 0; k < K; ++k) {
+        if (algos[k] < 0 || algos[k] > 2)
+            return fail(OCX_E_INVALID, "algos[" + std::to_string(k) + "] = " +
+                                           std::to_string(algos[k]) +
+                                           ": must be 0 (FTRL), 1 (FTL) or 2 (SMART)");
+        if (algos[k] == 2 && !thresh && B > 0)
+            return fail(OCX_E_INVALID, "a SMART column needs thresh");
+    }
+    return OCX_OK;
+}
+
+static int twin32_cols_check_lds(const ocx_layout* L, const int64_t* horizons, int64_t K) {
+    const int64_t hmax = ocx_twin32_cols_max_horizon(L);
+    if (K > 0 && horizons[K - 1] > hmax)
+        return fail(OCX_E_UNSUPPORTED,
+                    "horizon " + std::to_string(horizons[K - 1]) + " exceeds the " +
+                        std::to_string(hmax) + " rows of d = " + std::to_string(L->d) +
+                        " that fit the LDS (one wavefront per sequence; no lane fallback)");
+    return OCX_OK;
+}
+
+// group 0: the dispatcher's choice
+static int dev_twin32_cols(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                           int64_t K, const int64_t* horizons, const int32_t* algos, double eta0,
+                           const double* thresh, float* result, double* cum_loss,
+                           float* comp_loss, int64_t* switch_step, int group, void* stream) {
+    StreamDevice sd_(stream);
+    if (int rc = twin32_cols_check_layout(L)) return rc;
+    if (group != 0 && group != 1 && group != 2 && group != 4 && group != 8)
+        return fail(OCX_E_INVALID, "group must be 1, 2, 4 or 8");
+    if (group > ocx_twin32_cols_max_group(L))
+        return fail(OCX_E_UNSUPPORTED, "no group-" + std::to_string(group) + " form at " +
+                                           std::to_string(L->C) + " coordinates per lane");
+    if (int rc = twin32_cols_check_lists(horizons, algos, K, L->T, thresh, L->B)) return rc;
+    if (int rc = twin32_cols_check_lds(L, horizons, K)) return rc;
+    if (K == 0 || L->B == 0) return OCX_OK;
+    if (!result) return fail(OCX_E_INVALID, "NULL result");
+    if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL input buffer");
+    if (group == 0) group = twin32_cols_group_for(L, K);
+    OCX_HIP(ocx_launch_twin32_cols(L, z_tiled, y_tiled, K, horizons, algos, eta0, thresh, result,
+                                   cum_loss, comp_loss, switch_step, group, (hipStream_t)stream));
+    return OCX_OK;
+}
+
+int ocx_twin32_cols_group(const ocx_layout* L, int64_t K) {
+    if (int rc = twin32_cols_check_layout(L)) return rc;
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    return twin32_cols_group_for(L, K);
+}
+
+int ocx_dev_twin32_cols(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                        int64_t K, const int64_t* horizons, const int32_t* algos, double eta0,
+                        const double* thresh, float* result, double* cum_loss, float* comp_loss,
+                        int64_t* switch_step, void* stream) {
+    return dev_twin32_cols(L, z_tiled, y_tiled, K, horizons, algos, eta0, thresh, result, cum_loss,
+                           comp_loss, switch_step, 0, stream);
+}
+
+int ocx_test_twin32_cols(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                         int64_t K, const int64_t* horizons, const int32_t* algos, double eta0,
+                         const double* thresh, float* result, double* cum_loss, float* comp_loss,
+                         int64_t* switch_step, int group, void* stream) {
+    if (group != 1 && group != 2 && group != 4 && group != 8)
+        return fail(OCX_E_INVALID, "group must be 1, 2, 4 or 8");
+    return dev_twin32_cols(L, z_tiled, y_tiled, K, horizons, algos, eta0, thresh, result, cum_loss,
+                           comp_loss, switch_step, group, stream);
+}
+
+int ocx_twin32_cols_batch(const float* z, const float* y, int64_t B, int64_t T, int64_t d,
+                          int64_t K, const int64_t* horizons, const int32_t* algos, double eta0,
+                          const double* thresh, float* result, double* cum_loss, float* comp_loss,
+                          int64_t* switch_step, int device) {
+    if (B < 0 || T < 0 || d < 0) return fail(OCX_E_INVALID, "negative size");
+    if (d > 32) return fail(OCX_E_UNSUPPORTED, "the float32 twin supports d <= 32");
+    ocx_layout L;
+    if (int rc = ocx_layout_init(B, T, d, -1, &L)) return rc;  // one lane per sequence
+    // before anything is queued
+    if (int rc = twin32_cols_check_lists(horizons, algos, K, T, thresh, B)) return rc;
+    if (int rc = twin32_cols_check_lds(&L, horizons, K)) return rc;
+    if (B == 0 || K == 0) return OCX_OK;
+    if ((T * d > 0 && !z) || (T > 0 && !y) || !result) return fail(OCX_E_INVALID, "NULL argument");
+    DevCtx* cx;
+    if (int rc = ctx_enter(device, &cx)) return rc;
+    std::lock_guard<std::mutex> lk(cx->mu);
+    hipStream_t st = cx->stream;
+    const size_t nz = (size_t)(B * T * d), ny = (size_t)(B * T), nm = (size_t)(B * K);
+    OCX_HIP(cx->zraw.ensure(nz * 4));
+    OCX_HIP(cx->yraw.ensure(ny * 4));
+    OCX_HIP(cx->zt.ensure((size_t)L.z_elems * 8));
+    OCX_HIP(cx->yt.ensure((size_t)L.y_elems * 8));
+    OCX_HIP(cx->out.ensure(nm * 16));
+    OCX_HIP(cx->sw.ensure(nm * 8));
+    if (nz) OCX_HIP(hipMemcpyAsync(cx->zraw.p, z, nz * 4, hipMemcpyHostToDevice, st));
+    if (ny) OCX_HIP(hipMemcpyAsync(cx->yraw.p, y, ny * 4, hipMemcpyHostToDevice, st));
+    const double* dthr = nullptr;
+    if (thresh) {
+        OCX_HIP(cx->thr.ensure(nm * 8));
+        OCX_HIP(hipMemcpyAsync(cx->thr.p, thresh, nm * 8, hipMemcpyHostToDevice, st));
+        dthr = cx->thr.as<double>();
+    }
+    OCX_HIP(ocx_launch_pack32(&L, cx->zraw.as<float>(), cx->yraw.as<float>(), cx->zt.as<double>(),
+                              cx->yt.as<double>(), st));
+    double* cum = cx->out.as<double>();
+    float* res = reinterpret_cast<float*>(cum + nm);
+    float* comp = res + nm;
+    if (int rc = ocx_dev_twin32_cols(&L, cx->zt.as<double>(), cx->yt.as<double>(), K, horizons,
+                                     algos, eta0, dthr, res, cum, comp, cx->sw.as<int64_t>(), st))
+        return rc;
+    OCX_HIP(hipMemcpyAsync(result, res, nm * 4, hipMemcpyDeviceToHost, st));
+    if (cum_loss) OCX_HIP(hipMemcpyAsync(cum_loss, cum, nm * 8, hipMemcpyDeviceToHost, st));
+    if (comp_loss) OCX_HIP(hipMemcpyAsync(comp_loss, comp, nm * 4, hipMemcpyDeviceToHost, st));
+    if (switch_step)
+        OCX_HIP(hipMemcpyAsync(switch_step, cx->sw.p, nm * 8, hipMemcpyDeviceToHost, st));
+    OCX_HIP(hipStreamSynchronize(st));
+    return OCX_OK;
+}
+
 int ocx_twin32_gT_regrets(uint64_t base_seed, int64_t T, int64_t run0, int64_t R, int64_t d,
                           double eta0, float* regrets, int device) {
     if (R < 0 || run0 < 0 || T < 0 || d < 0) return fail(OCX_E_INVALID, "negative argument");

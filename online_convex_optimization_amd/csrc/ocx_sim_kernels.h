@@ -236,6 +236,18 @@ hipError_t ocx_launch_twin32(const ocx_layout* L, const double* zt, const double
                              double* cum, float* comp, int64_t* sw, hipStream_t st);
 hipError_t ocx_launch_pack32(const ocx_layout* L, const float* z, const float* y, double* zt,
                              double* ytl, hipStream_t st);
+// Its column form (ocx_twin32_cols.hip): K columns (hz[k], algos[k], thresh[b][k]), hz / algos
+// HOST arrays the caller has validated (hz non-decreasing in [0, T], algos in 0..2), in launches
+// of `group` (1, 2, 4, 8; <= ocx_twin32_cols_max_group) consecutive columns; one wavefront per
+// sequence, rows [0, group's last horizon) staged in LDS.  result [B][K]; cum / comp / sw
+// [B][K] nullable.  hipErrorNotSupported, before any launch, when hz[K - 1] exceeds
+// ocx_twin32_cols_max_horizon(L).
+int ocx_twin32_cols_max_group(const ocx_layout* L);
+int64_t ocx_twin32_cols_max_horizon(const ocx_layout* L);
+hipError_t ocx_launch_twin32_cols(const ocx_layout* L, const double* zt, const double* yt,
+                                  int64_t K, const int64_t* hz, const int32_t* algos, double eta0,
+                                  const double* thresh, float* result, double* cum, float* comp,
+                                  int64_t* sw, int group, hipStream_t st);
 // exact_ftl.py:224-227 `_comparator_loss` in OpenBLAS / NumPy order (ocx_comp_blas.hip):
 // z [B][T][d] and y [B][T] row-major, x [B][d]; absr scratch [B][T]
 hipError_t ocx_launch_comp_blas(const double* z, const double* y, const double* x, int64_t B,

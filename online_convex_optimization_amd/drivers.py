@@ -152,10 +152,55 @@ def case_regrets_twin32(title: str, T: int, g_emp_T: float, *, runs: int, replic
     rep_idx = np.tile(np.arange(replicates), runs)
     db.generate_family(family, base_seed + 2025 * (run_idx + 1), stream0 + rep_idx, p=p,
                        block_len=block_len)
-    out = {"FTRL": db.simulate_twin32(0, SQRT2), "FTL": db.simulate_twin32(1, SQRT2),
-           "SMART": db.simulate_twin32(2, SQRT2, math.sqrt(2 * T)),
-           "EMP": db.simulate_twin32(2, SQRT2, float(g_emp_T))}  # driver.py:95 float(g_emp[T])
-    return {k: v[:B].cpu().numpy().reshape(runs, replicates) for k, v in out.items()}
+    # The four lines share one staging of the rows and one prefix re-scan per step: one
+    # 4-column call, the bits of four simulate_twin32 launches
+    th = [math.sqrt(2 * T), float(g_emp_T)]  # driver.py:95 float(g_emp[T])
+    try:
+        res = db.simulate_twin32_cols([T] * 4, [0, 1, 2, 2], [np.nan, np.nan, *th],
+                                      SQRT2)["result"][:B].cpu().numpy()
+    except NotImplementedError:  # T rows do not fit the LDS: the single calls' lane kernel
+        out = {"FTRL": db.simulate_twin32(0, SQRT2), "FTL": db.simulate_twin32(1, SQRT2),
+               "SMART": db.simulate_twin32(2, SQRT2, th[0]),
+               "EMP": db.simulate_twin32(2, SQRT2, th[1])}
+        return {k: v[:B].cpu().numpy().reshape(runs, replicates) for k, v in out.items()}
+    return {k: res[:, i].reshape(runs, replicates) for i, k in enumerate(ALGO_KEYS)}
+
+
+def driver_case_regret_curves(title: str, T_grid: Sequence[int], g_emp: Mapping[int, float], *,
+                              runs: int, replicates: int, base_seed: int = 0, d: int = 5,
+                              p: float = 0.10, block_len: int = 20, device: int = 0
+                              ) -> Dict[str, np.ndarray]:
+    """The four lines of case_regrets_twin32 against the horizon, from ONE batch: the case's
+    sequences are generated once at horizon max(T_grid) and the float32 twin is read at every
+    T of ``T_grid`` (strictly increasing) by one column call
+    (DeviceBatch.twin32_comparison_curves: 4K columns, one staging of the rows and one prefix
+    re-scan per step for a group of them).  ``g_emp`` maps T to the empirical threshold, as
+    in driver_evaluate_stream_with_stats.  Returns {"FTRL", "FTL", "SMART", "EMP"}, float32
+    [runs * replicates, K] each; column k is the twin's regret on the first T_k rows of that
+    batch.
+
+    What the columns are depends on the family.  For the deterministic families (label flips,
+    switching leaders) the prefix of the long sequence IS the reference's sequence at each T,
+    so column k holds the reference's numbers: case_regrets_twin32(title, T_k, g_emp[T_k]),
+    bit for bit.  For the random families (i.i.d., Massart) the reference draws a fresh
+    sequence per T (sequence_generation.py:61-62: the generator is seeded with T), so the
+    curve is the anytime regret on the longest horizon's rows — a different sample of the
+    same distribution, not the reference's per-T numbers.
+    driver_evaluate_stream_with_stats therefore keeps one batch per T."""
+    family, stream0 = CASE_FAMILIES[title]
+    grid = np.asarray(T_grid)
+    ck = engine._checkpoints(grid, int(grid.max()) if grid.size else 0)  # ValueError if bad
+    B, K = runs * replicates, int(ck.size)
+    if B == 0 or K == 0:
+        return {k: np.zeros((B, K), dtype=np.float32) for k in ALGO_KEYS}
+    g = np.array([float(g_emp[int(T)]) for T in ck])  # driver.py:95 float(g_emp[T])
+    db = engine.DeviceBatch(B, int(ck[-1]), d, lanes_per_seq=-1, device=device)
+    run_idx = np.repeat(np.arange(runs), replicates)
+    rep_idx = np.tile(np.arange(replicates), runs)
+    db.generate_family(family, base_seed + 2025 * (run_idx + 1), stream0 + rep_idx, p=p,
+                       block_len=block_len)
+    out = db.twin32_comparison_curves(ck, g, SQRT2)
+    return {k: out[k][:B].cpu().numpy() for k in ALGO_KEYS}
 
 
 def driver_evaluate_stream_with_stats(title: str, T_grid: Sequence[int],

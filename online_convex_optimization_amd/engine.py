@@ -608,6 +608,101 @@ def twin32_batch(z, y, algo: int = 0, eta0: float = SQRT2, thresh=None, *, devic
     return (res, cum, comp, sw) if return_all else res
 
 
+def _twin32_algos(algos, K: int) -> np.ndarray:
+    """The algorithms of a twin column call as a contiguous int32 array [K]: a scalar (every
+    column the same) or a length-K list of 0 / 1 / 2 or the names of TWIN32_ALGOS.  Booleans,
+    other numbers and other names are rejected.  Raises ValueError otherwise."""
+    if isinstance(algos, (str, bytes)) or np.ndim(algos) == 0:
+        algos = [algos] * K
+    try:
+        items = list(algos)
+    except TypeError:
+        raise ValueError("algos must be a scalar or a one-dimensional list") from None
+    if len(items) != K:
+        raise ValueError(f"need one algorithm per horizon: {K} horizons, {len(items)} algorithms")
+    out = np.zeros(K, dtype=np.int32)
+    for k, a in enumerate(items):
+        if isinstance(a, str):
+            if a not in TWIN32_ALGOS:
+                raise ValueError(f"algos[{k}] = {a!r}: must be one of {sorted(TWIN32_ALGOS)}")
+            out[k] = TWIN32_ALGOS[a]
+        elif isinstance(a, (int, np.integer)) and not isinstance(a, (bool, np.bool_)) \
+                and int(a) in (0, 1, 2):
+            out[k] = int(a)
+        else:
+            raise ValueError(f"algos[{k}] = {a!r}: must be 0 (FTRL), 1 (FTL), 2 (SMART) or a "
+                             f"name of {sorted(TWIN32_ALGOS)}")
+    return out
+
+
+def _twin32_cols_thresholds(thresholds, hz: np.ndarray, al: np.ndarray, B: int):
+    """[B, K] float64 thresholds of a twin column call, or None when no column is SMART.
+    ``thresholds`` None: SMART's own sqrt(2 t_k) in the SMART columns.  Otherwise [K] or [B, K]
+    through _thresholds, one column per horizon; the entries of FTRL / FTL columns are ignored
+    (NaN is the natural filler), a NaN in a SMART column is a missing threshold: ValueError."""
+    smart = al == 2
+    if thresholds is None:
+        if not smart.any():
+            return None
+        thresholds = np.where(smart, np.sqrt(2.0 * hz.astype(np.float64)), 0.0)
+    th = _thresholds(thresholds, B)
+    if th.shape[1] != hz.size:
+        raise ValueError(f"need one threshold column per horizon: {hz.size} horizons, "
+                         f"{th.shape[1]} threshold columns")
+    if np.isnan(th[:, smart]).any():
+        raise ValueError("a SMART column needs a threshold: NaN in columns "
+                         f"{np.flatnonzero(smart & np.isnan(th).any(axis=0)).tolist()}")
+    th[:, ~smart] = 0.0
+    return th if smart.any() else None
+
+
+def _twin32_cols_call(call, name: str, *args) -> None:
+    """A twin column call; OCX_E_UNSUPPORTED (a horizon whose rows do not fit the LDS: the
+    library's message names the limit for that d) surfaces as NotImplementedError."""
+    try:
+        call(name, *args)
+    except _lib.OCXError as e:
+        if ": unsupported: " in str(e):
+            raise NotImplementedError(str(e)) from None
+        raise
+
+
+def twin32_cols_batch(z, y, horizons, algos=2, thresholds=None, eta0: float = SQRT2, *,
+                      device: int = 0, return_all: bool = False):
+    """Twin sweeps: the float32 twin (twin32_batch) over B sequences for K columns (horizon
+    t_k, algorithm, threshold) from one staging of the rows and one prefix re-scan per step
+    (ocx_twin32_cols_batch; csrc/ocx_twin32_cols.hip).
+
+    ``horizons`` [K]: integers, non-decreasing in [0, T], duplicates legal (FTRL, FTL, SMART
+    and EMP at the same t_k).  ``algos``: a scalar or a length-K list of 0 / 1 / 2 or "FTRL" /
+    "FTL" / "SMART" (TWIN32_ALGOS).  ``thresholds``: None (sqrt(2 t_k) in the SMART columns),
+    [K] or [B, K]; the entries of FTRL / FTL columns are ignored, NaN in a SMART column is an
+    error.  Column k is twin32_batch(z[:, :t_k], y[:, :t_k], algos[k], eta0,
+    thresh=thresholds[..., k]) bit for bit.  The rows of the last horizon must fit the LDS
+    (2194 rows at d = 5): NotImplementedError otherwise.  Returns float32 results [B, K] or,
+    with ``return_all``, (result, cum_loss float64, comp_loss float32, switch_step int64; -1 =
+    no switch / not SMART), each [B, K]."""
+    z = np.ascontiguousarray(z, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    B, T, d = _check_zy(z, y)
+    hz = _horizons(horizons, T)
+    K = int(hz.size)
+    al = _twin32_algos(algos, K)
+    th = _twin32_cols_thresholds(thresholds, hz, al, B)
+    res = np.zeros((B, K), dtype=np.float32)
+    cum = np.zeros((B, K)) if return_all else None
+    comp = np.zeros((B, K), dtype=np.float32) if return_all else None
+    sw = np.full((B, K), -1, dtype=np.int64) if return_all else None
+    fp = _lib.c_fp
+    _twin32_cols_call(_lib.call, "ocx_twin32_cols_batch", z.ctypes.data_as(fp),
+                      y.ctypes.data_as(fp), B, T, d, K, hz.ctypes.data_as(_lib.c_i64p),
+                      al.ctypes.data_as(_lib.c_i32p), float(eta0), ptr(th),
+                      res.ctypes.data_as(fp), ptr(cum),
+                      comp.ctypes.data_as(fp) if comp is not None else None,
+                      sw.ctypes.data_as(_lib.c_i64p) if sw is not None else None, int(device))
+    return (res, cum, comp, sw) if return_all else res
+
+
 def twin32_gT_regrets(T: int, runs: int, *, base_seed: int = 0, d: int = 5,
                       eta0: float = SQRT2, run0: int = 0, device: int = 0) -> np.ndarray:
     """The float32 twin's g(T) regrets (algorithms.py:150-169) for runs [run0, run0+runs),
@@ -1038,6 +1133,70 @@ class DeviceBatch:
         if th is not None:
             self._keep_th = self._hold(th)
         return res
+
+    def simulate_twin32_cols(self, horizons, algos=2, thresholds=None, eta0: float = SQRT2, *,
+                             _group=None):
+        """Twin sweeps on the resident batch (ocx_dev_twin32_cols, async; one-lane layout,
+        ``lanes_per_seq=-1``): the float32 twin for K columns (horizon t_k, algorithm,
+        threshold), ocx_twin32_cols_group(L, K) consecutive columns per launch, each launch
+        staging the rows of its last horizon once and re-scanning the prefix once per step for
+        all its columns.  Arguments as twin32_cols_batch (validated here).  Returns a dict of
+        device tensors, each [B, K]: ``result`` float32, ``cum`` float64, ``comp`` float32,
+        ``switch_step`` int64 (-1 = never, and every FTRL / FTL column); column k is what
+        simulate_twin32(algos[k], eta0, thresholds[..., k]) gives on a batch of the first t_k
+        rows, bit for bit.  A last horizon whose rows do not fit the LDS raises
+        NotImplementedError.  (``_group``: tests force the columns per launch through
+        include/ocx_testing.h.)"""
+        torch = self.torch
+        B = int(self.L.B)
+        hz = _horizons(horizons, self.L.T)
+        K = int(hz.size)
+        al = _twin32_algos(algos, K)
+        tha = _twin32_cols_thresholds(thresholds, hz, al, B)
+        with torch.cuda.device(self.device), self._on_stream():
+            th = torch.as_tensor(tha).to(self.device) if tha is not None else None
+            out = {"result": torch.zeros((B, K), dtype=torch.float32, device=self.device),
+                   "cum": torch.zeros((B, K), dtype=torch.float64, device=self.device),
+                   "comp": torch.zeros((B, K), dtype=torch.float32, device=self.device),
+                   "switch_step": torch.full((B, K), -1, dtype=torch.int64, device=self.device)}
+        some = B * K > 0
+        args = (self._lp(), self.z.data_ptr(), self.y.data_ptr(), K,
+                hz.ctypes.data_as(_lib.c_i64p), al.ctypes.data_as(_lib.c_i32p), float(eta0),
+                th.data_ptr() if th is not None and some else None,
+                *(out[k].data_ptr() if some else None
+                  for k in ("result", "cum", "comp", "switch_step")))
+        if _group is None:
+            _twin32_cols_call(self._call, "ocx_dev_twin32_cols", *args, self._sp)
+        else:
+            _twin32_cols_call(self._call, "ocx_test_twin32_cols", *args, int(_group), self._sp)
+        if th is not None:
+            self._keep_th = self._hold(th)
+        return out
+
+    def twin32_comparison_curves(self, checkpoints, g_emp=None, eta0: float = SQRT2):
+        """The four lines of driver.py's comparison figure (driver.py:70-136, the float32 twin)
+        against the horizon, from this resident batch: a dict of float32 [B, K] device tensors
+        ``FTRL``, ``FTL``, ``SMART`` (threshold sqrt(2 t_k)) and, when ``g_emp`` ([K], the
+        empirical g(t_k)) is given, ``EMP`` — ONE simulate_twin32_cols call over the 3K or 4K
+        columns sorted by horizon.  ``checkpoints`` is strictly increasing in [0, T].  Column
+        k of each is the twin's result on the batch truncated at t_k."""
+        ck = _checkpoints(checkpoints, self.L.T)
+        K = int(ck.size)
+        nan = np.full(K, np.nan)
+        cols = [("FTRL", 0, nan), ("FTL", 1, nan),
+                ("SMART", 2, np.sqrt(2.0 * ck.astype(np.float64)))]
+        if g_emp is not None:
+            g = _etas(g_emp)
+            if g.shape != (K,):
+                raise ValueError(f"g_emp must be [K = {K}], got shape {g.shape}")
+            cols.append(("EMP", 2, g))
+        n = len(cols)
+        hz = np.repeat(ck, n)                                    # t_0 × n, t_1 × n, ...
+        al = np.tile(np.array([c[1] for c in cols], dtype=np.int32), K)
+        th = np.stack([c[2] for c in cols], axis=1).reshape(-1)  # interleaved the same way
+        res = self.simulate_twin32_cols(hz, al, th, eta0)["result"]
+        with self._on_stream():
+            return {name: res[:, i::n].contiguous() for i, (name, _, _) in enumerate(cols)}
 
     def ftl_exact(self, cmp_action=None, regime=None, norm: str = "l2"):
         """Exact FTL (l2 ball, closed form; see ftl_exact_batch) on the resident batch:
