@@ -65,7 +65,10 @@
  * ocx_simulate_smart_curve_batch), and for the FTRL-vs-exact-FTL regret-curve symbols
  * (ocx_ftrl_exact_curve_workspace_bytes, ocx_dev_ftrl_vs_exact_curve,
  * ocx_ftrl_vs_exact_curve_batch), and for the float32 twin's column symbols
- * (ocx_twin32_cols_group, ocx_dev_twin32_cols, ocx_twin32_cols_batch).
+ * (ocx_twin32_cols_group, ocx_dev_twin32_cols, ocx_twin32_cols_batch), and for the regret-grid
+ * symbols (ocx_curve_etas_group, ocx_curve_etas_workspace_bytes,
+ * ocx_dev_simulate_alg_curve_etas, ocx_simulate_alg_curve_etas_batch,
+ * ocx_dev_max_regret_cols).
  *
  * Checking the ABI: one intermediate 0.1.x tree exported ocx_ftrl_vs_exact_batch WITH a
  * `norm` argument under the same symbol and the same version number as the release without
@@ -468,6 +471,74 @@ int ocx_simulate_alg_etas_batch(const double* z, const double* y, int64_t B, int
                                 const double* etas, int64_t M, double* regret, double* cum_loss,
                                 double* comp_loss, int32_t* closed_out, int lanes_per_seq,
                                 int device);
+
+/* Regret grids: FTRL (alg_flag 0) for M values of eta0, each observed at K checkpoint horizons,
+ * in passes over z that each serve a group of step sizes — the step-size sweep and the regret
+ * curve in one call.  For step sizes etas[M] (any values, any order, duplicates allowed) and
+ * checkpoints 0 <= t_1 < ... < t_K <= T, the outputs are [B][M][K] row-major and
+ *   regret[b][m][k], cum_loss[b][m][k], comp_loss[b][m][k], closed_out[b][m][k]
+ * are bit for bit what ocx_dev_simulate_alg_ex gives with alg_flag 0, eta0 = etas[m],
+ * comparator = x_last = NULL on (z[b][:t_k], y[b][:t_k]) in the same layout and with the same
+ * flags.  So [:, m, :] is ocx_dev_simulate_alg_curve with eta0 = etas[m], and where t_K = T,
+ * [:, :, K-1] is ocx_dev_simulate_alg_etas; the result does not depend on the group size in
+ * use.  FTRL only (FTL has no step size); no caller comparator, no x_last.
+ *
+ * step sizes one pass over z serves in layout L (1: one pass per step size; negative
+ * ocx_status on error).  ocx_etas_group's rule, less two chained instances that are not
+ * compiled, and 2 instead of 4 for the pipelined 8-lane layout at 4 coordinates per lane,
+ * where 4 measured slower than 2; every other class of layouts measured the largest group
+ * fastest against M curve calls; never above the smallest group that holds
+ * M. */
+int ocx_curve_etas_group(const ocx_layout* L, int64_t M);
+
+/* bytes of caller-owned device workspace for K checkpoints and M step sizes in layout L:
+ * G * K * min(group, M) * 64 * (8 C + 12), one pass's theta, cum and need words, reused by the
+ * next group of step sizes on the same stream (0 for K == 0 or M == 0; negative ocx_status on
+ * error) */
+int64_t ocx_curve_etas_workspace_bytes(const ocx_layout* L, int64_t K, int64_t M);
+
+/* device: etas is a HOST array [M], read at call time (it travels in the kernel arguments);
+ * checkpoints is a DEVICE int64 array [K], strictly increasing in [0, L->T] — a precondition
+ * the call cannot see: an array that breaks it gives meaningless numbers, but the kernels
+ * never leave the batch, the outputs and the workspace whatever it holds;
+ * regret / cum_loss / comp_loss: device [B][M][K] row-major, each nullable;
+ * closed_out [B][M][K] int32 nullable (1 = closed form taken);
+ * flags: 0, or OCX_ALG_CLOSED_COMPARATOR / OCX_ALG_CLIPPED_ROWS (one request, as in
+ * ocx_dev_simulate_alg_ex).  The certificate is per (sequence, eta, prefix): the row check is
+ * shared across columns, the sub-gradient check is per column, both "so far" at each
+ * checkpoint; a triple it cannot certify gets the streamed pass over its own prefix (the
+ * rows read once per (wave-group, checkpoint) for all of a pass's columns), bit-identical to
+ * flags 0, and a certified triple keeps the closed form whatever shares its wave, its launch
+ * or its group;
+ * workspace: workspace_bytes >= ocx_curve_etas_workspace_bytes(L, K, M) of device memory,
+ * 8-byte aligned, the call's own until the stream has passed it; too small is OCX_E_INVALID
+ * and nothing is launched;
+ * M == 0, K == 0, B == 0 and T == 0 are valid and launch nothing or next to nothing (t_k = 0
+ * gives zeros);
+ * asynchronous, no allocation, no sync: capture-safe like the other dev entry points. */
+int ocx_dev_simulate_alg_curve_etas(const ocx_layout* L, const double* z_tiled,
+                                    const double* y_tiled, const double* etas, int64_t M,
+                                    const int64_t* checkpoints, int64_t K, double* regret,
+                                    double* cum_loss, double* comp_loss, int32_t* closed_out,
+                                    int flags, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+
+/* host: numpy buffers in, [B][M][K] out; etas and checkpoints are HOST arrays; M >= 0,
+ * K >= 0 and the checkpoints' order and range are validated here before any device is touched.
+ * Bit-exact layouts (lanes_per_seq 1 / -k): streamed comparator for every triple;
+ * other modes: closed form where certified. */
+int ocx_simulate_alg_curve_etas_batch(const double* z, const double* y, int64_t B, int64_t T,
+                                      int64_t d, const double* etas, int64_t M,
+                                      const int64_t* checkpoints, int64_t K, double* regret,
+                                      double* cum_loss, double* comp_loss, int32_t* closed_out,
+                                      int lanes_per_seq, int device);
+
+/* column-wise ocx_dev_max_regret: gmax[n] = max(start, max_b regrets[b][n]) over the device
+ * array regrets [B][N] row-major, start = +0.0, or with accumulate != 0 what gmax[n] holds (so
+ * batches accumulate).  The `reg > max` scan of ocx_dev_max_regret per column: a column of
+ * negative regrets gives +0.0 and NaNs are ignored.  gmax: device [N].  Asynchronous. */
+int ocx_dev_max_regret_cols(const double* regrets, int64_t B, int64_t N, double* gmax,
+                            int accumulate, void* stream);
 
 /* ocx_ftl_exact_batch on device (`norm` 0 l2, 1 l1, 2 linf). */
 int ocx_dev_ftl_exact(const ocx_layout* L, const double* z_tiled, const double* y_tiled, int norm,

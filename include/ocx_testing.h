@@ -70,6 +70,17 @@ int ocx_test_simulate_alg_etas(const ocx_layout* L, const double* z_tiled, const
                                double* comp_loss, int32_t* closed_out, int flags, int group,
                                void* stream);
 
+/* ocx_dev_simulate_alg_curve_etas with the group size forced to `group` (1, 2 or 4) instead of
+ * ocx_curve_etas_group's choice.  OCX_E_UNSUPPORTED where that form is not instantiated for
+ * the layout (group 2 above 16 coordinates per lane, group 4 above 8).  The workspace holds
+ * G * K * min(group, M) * 64 * (8 C + 12) bytes.  Asynchronous like the product call. */
+int ocx_test_simulate_alg_curve_etas(const ocx_layout* L, const double* z_tiled,
+                                     const double* y_tiled, const double* etas, int64_t M,
+                                     const int64_t* checkpoints, int64_t K, double* regret,
+                                     double* cum_loss, double* comp_loss, int32_t* closed_out,
+                                     int flags, int group, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+
 /* ocx_dev_simulate_smart_thresholds with the group size forced to `group` (1, 2 or 4) instead
  * of ocx_smart_thresholds_group's choice.  OCX_E_UNSUPPORTED where that form is not
  * instantiated for the layout (group 2 above 16 coordinates per lane, group 4 above 8).

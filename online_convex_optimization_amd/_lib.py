@@ -103,6 +103,15 @@ SIGNATURES = {
     "ocx_simulate_alg_etas_batch": (c_int, [c_dp, c_dp, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp,
                                             c_dp, c_dp, ctypes.POINTER(ctypes.c_int32), c_int,
                                             c_int]),
+    "ocx_curve_etas_group": (c_int, [ctypes.POINTER(Layout), c_i64]),
+    "ocx_curve_etas_workspace_bytes": (c_i64, [ctypes.POINTER(Layout), c_i64, c_i64]),
+    "ocx_dev_simulate_alg_curve_etas": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_dp, c_i64,
+                                                c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp,
+                                                ctypes.c_size_t, c_vp]),
+    "ocx_simulate_alg_curve_etas_batch": (c_int, [c_dp, c_dp, c_i64, c_i64, c_i64, c_dp, c_i64,
+                                                  c_i64p, c_i64, c_dp, c_dp, c_dp,
+                                                  ctypes.POINTER(ctypes.c_int32), c_int, c_int]),
+    "ocx_dev_max_regret_cols": (c_int, [c_vp, c_i64, c_i64, c_vp, c_int, c_vp]),
     "ocx_smart_thresholds_group": (c_int, [ctypes.POINTER(Layout), c_i64]),
     "ocx_dev_simulate_smart_thresholds": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_vp, c_i64,
                                                   c_double, c_vp, c_vp, c_int, c_vp, c_vp]),
@@ -158,6 +167,9 @@ TEST_SIGNATURES = {
                                              c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "ocx_test_simulate_alg_etas": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_dp, c_i64, c_vp,
                                            c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
+    "ocx_test_simulate_alg_curve_etas": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_dp, c_i64,
+                                                 c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
+                                                 c_vp, ctypes.c_size_t, c_vp]),
     "ocx_test_simulate_smart_thresholds": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_vp, c_i64,
                                                    c_double, c_vp, c_vp, c_int, c_vp, c_int,
                                                    c_vp]),

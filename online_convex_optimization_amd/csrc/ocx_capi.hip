@@ -483,6 +483,98 @@ int ocx_test_simulate_alg_etas(const ocx_layout* L, const double* z_tiled, const
                                  closed_out, flags, group, stream);
 }
 
+// the smallest instantiated grid group that holds M step sizes, capped at `best`
+static int grid_group_for(const ocx_layout* L, int64_t M, int best) {
+    int g = best;
+    while (g > 1 && (g / 2 >= M || !ocx_grid_instance(L, g))) g /= 2;
+    return g;
+}
+
+int ocx_curve_etas_group(const ocx_layout* L, int64_t M) {
+    if (int rc = check_layout(L)) return rc;
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    return grid_group_for(L, M, ocx_grid_best_group(L));
+}
+
+// workspace of a call whose passes hold at most `group` step sizes
+static int64_t grid_workspace_bytes(const ocx_layout* L, int64_t K, int64_t M, int group) {
+    if (int rc = check_layout(L)) return rc;
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    if (L->B < 0 || L->T < 0 || L->G != ceil_div(L->B, L->S))
+        return fail(OCX_E_INVALID, "corrupt layout");
+    // strictly increasing checkpoints in [0, T]: at most T + 1 of them (bounds the product)
+    if (K > L->T + 1) return fail(OCX_E_INVALID, "more checkpoints than horizons 0..T");
+    return ocx_grid_ws_bytes(L, K, M < group ? M : group);
+}
+
+int64_t ocx_curve_etas_workspace_bytes(const ocx_layout* L, int64_t K, int64_t M) {
+    if (int rc = check_layout(L)) return rc;
+    return grid_workspace_bytes(L, K, M, ocx_grid_best_group(L));
+}
+
+// group 0: the dispatcher's choice
+static int dev_simulate_alg_curve_etas(const ocx_layout* L, const double* z_tiled,
+                                       const double* y_tiled, const double* etas, int64_t M,
+                                       const int64_t* checkpoints, int64_t K, double* regret,
+                                       double* cum_loss, double* comp_loss, int32_t* closed_out,
+                                       int flags, int group, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    StreamDevice sd_(stream);
+    if (int rc = check_layout(L)) return rc;
+    if (group != 0 && group != 1 && group != 2 && group != 4)
+        return fail(OCX_E_INVALID, "group must be 1, 2 or 4");
+    if (group != 0 && !ocx_grid_instance(L, group))
+        return fail(OCX_E_UNSUPPORTED, "no group-" + std::to_string(group) + " form at " +
+                                           std::to_string(L->C) + " coordinates per lane");
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    if (group == 0) group = grid_group_for(L, M, ocx_grid_best_group(L));
+    const int64_t need = grid_workspace_bytes(L, K, M, group);  // checks K too
+    if (need < 0) return (int)need;
+    if (M > 0 && !etas) return fail(OCX_E_INVALID, "NULL etas");
+    if (flags & ~(OCX_ALG_CLIPPED_ROWS | OCX_ALG_CLOSED_COMPARATOR))
+        return fail(OCX_E_INVALID, "unknown flags");
+    if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL input buffer");
+    if (K > 0 && !checkpoints) return fail(OCX_E_INVALID, "NULL checkpoints");
+    if (need > 0 && (!workspace || workspace_bytes < (size_t)need))
+        return fail(OCX_E_INVALID,
+                    "workspace smaller than ocx_curve_etas_workspace_bytes(L, K, M) = " +
+                        std::to_string(need));
+    if (need > 0 && (reinterpret_cast<uintptr_t>(workspace) & 7) != 0)
+        return fail(OCX_E_INVALID, "workspace is not 8-byte aligned");
+    if (M == 0 || K == 0 || L->B == 0) return OCX_OK;
+    // the two flags are one request: the kernel certifies every row and sub-gradient itself
+    OCX_HIP(ocx_launch_alg_grid(L, z_tiled, y_tiled, etas, M, checkpoints, K, regret, cum_loss,
+                                comp_loss, closed_out,
+                                (flags & (OCX_ALG_CLIPPED_ROWS | OCX_ALG_CLOSED_COMPARATOR)) ? 1 : 0,
+                                group, workspace, (hipStream_t)stream));
+    return OCX_OK;
+}
+
+int ocx_dev_simulate_alg_curve_etas(const ocx_layout* L, const double* z_tiled,
+                                    const double* y_tiled, const double* etas, int64_t M,
+                                    const int64_t* checkpoints, int64_t K, double* regret,
+                                    double* cum_loss, double* comp_loss, int32_t* closed_out,
+                                    int flags, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    return dev_simulate_alg_curve_etas(L, z_tiled, y_tiled, etas, M, checkpoints, K, regret,
+                                       cum_loss, comp_loss, closed_out, flags, 0, workspace,
+                                       workspace_bytes, stream);
+}
+
+int ocx_test_simulate_alg_curve_etas(const ocx_layout* L, const double* z_tiled,
+                                     const double* y_tiled, const double* etas, int64_t M,
+                                     const int64_t* checkpoints, int64_t K, double* regret,
+                                     double* cum_loss, double* comp_loss, int32_t* closed_out,
+                                     int flags, int group, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    if (group != 1 && group != 2 && group != 4)
+        return fail(OCX_E_INVALID, "group must be 1, 2 or 4");
+    return dev_simulate_alg_curve_etas(L, z_tiled, y_tiled, etas, M, checkpoints, K, regret,
+                                       cum_loss, comp_loss, closed_out, flags, group, workspace,
+                                       workspace_bytes, stream);
+}
+
 int ocx_dev_ftl_exact(const ocx_layout* L, const double* z_tiled, const double* y_tiled, int norm,
                       double* cum_loss, double* comp_loss, double* cmp_action, int32_t* regime,
                       void* stream) {
@@ -831,6 +923,17 @@ int ocx_dev_max_regret(const double* regrets, int64_t B, double* gmax, void* str
     return OCX_OK;
 }
 
+int ocx_dev_max_regret_cols(const double* regrets, int64_t B, int64_t N, double* gmax,
+                            int accumulate, void* stream) {
+    StreamDevice sd_(stream);
+    if (B < 0 || N < 0) return fail(OCX_E_INVALID, "negative B / N");
+    if (N == 0) return OCX_OK;
+    if (!gmax || (B > 0 && !regrets)) return fail(OCX_E_INVALID, "NULL buffer");
+    OCX_HIP(ocx_launch_max_cols(regrets, B, N, gmax, accumulate != 0 ? 1 : 0,
+                                (hipStream_t)stream));
+    return OCX_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -1023,6 +1126,66 @@ int ocx_simulate_alg_etas_batch(const double* z, const double* y, int64_t B, int
     if (cum_loss) std::memcpy(cum_loss, h.data() + nm, nm * 8);
     if (comp_loss) std::memcpy(comp_loss, h.data() + 2 * nm, nm * 8);
     if (closed_out) std::memcpy(closed_out, h.data() + 3 * nm, nm * 4);
+    return OCX_OK;
+}
+
+int ocx_simulate_alg_curve_etas_batch(const double* z, const double* y, int64_t B, int64_t T,
+                                      int64_t d, const double* etas, int64_t M,
+                                      const int64_t* checkpoints, int64_t K, double* regret,
+                                      double* cum_loss, double* comp_loss, int32_t* closed_out,
+                                      int lanes_per_seq, int device) {
+    ocx_layout L;
+    if (int rc = ocx_layout_init(B, T, d, lanes_per_seq, &L)) return rc;
+    // everything about the step sizes and the checkpoints before any device or data pointer
+    // is touched
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    if (M > 0 && !etas) return fail(OCX_E_INVALID, "NULL etas");
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    if (K > 0 && !checkpoints) return fail(OCX_E_INVALID, "NULL checkpoints");
+    for (int64_t k = 0; k < K; ++k) {
+        if (checkpoints[k] < 0 || checkpoints[k] > T)
+            return fail(OCX_E_INVALID, "checkpoint " + std::to_string(checkpoints[k]) +
+                                           " outside [0, T = " + std::to_string(T) + "]");
+        if (k > 0 && checkpoints[k] <= checkpoints[k - 1])
+            return fail(OCX_E_INVALID, "checkpoints must be strictly increasing");
+    }
+    if (B == 0 || M == 0 || K == 0) return OCX_OK;
+    if ((T * d > 0 && !z) || (T > 0 && !y)) return fail(OCX_E_INVALID, "NULL z/y");
+    const int64_t wsb = ocx_curve_etas_workspace_bytes(&L, K, M);
+    if (wsb < 0) return (int)wsb;
+    DevCtx* cx;
+    if (int rc = ctx_enter(device, &cx)) return rc;
+    std::lock_guard<std::mutex> lk(cx->mu);
+    hipStream_t st = cx->stream;
+    const size_t nz = (size_t)(B * T * d), ny = (size_t)(B * T), nk = (size_t)(B * M * K);
+    OCX_HIP(cx->zraw.ensure(nz * 8));
+    OCX_HIP(cx->yraw.ensure(ny * 8));
+    OCX_HIP(cx->zt.ensure((size_t)L.z_elems * 8));
+    OCX_HIP(cx->yt.ensure((size_t)L.y_elems * 8));
+    OCX_HIP(cx->out.ensure(nk * (3 * 8 + 4)));
+    OCX_HIP(cx->sw.ensure((size_t)K * 8));
+    OCX_HIP(cx->theta.ensure((size_t)wsb));
+    if (nz) OCX_HIP(hipMemcpyAsync(cx->zraw.p, z, nz * 8, hipMemcpyHostToDevice, st));
+    if (ny) OCX_HIP(hipMemcpyAsync(cx->yraw.p, y, ny * 8, hipMemcpyHostToDevice, st));
+    OCX_HIP(hipMemcpyAsync(cx->sw.p, checkpoints, (size_t)K * 8, hipMemcpyHostToDevice, st));
+    OCX_HIP(ocx_launch_pack(&L, cx->zraw.as<double>(), cx->yraw.as<double>(), cx->zt.as<double>(),
+                            cx->yt.as<double>(), st));
+    double* o = cx->out.as<double>();
+    int32_t* oc = reinterpret_cast<int32_t*>(o + 3 * nk);
+    // bit-exact modes keep the reference's streamed comparator sum for every triple
+    const int flags = (lanes_per_seq == 1 || lanes_per_seq < 0) ? 0 : OCX_ALG_CLOSED_COMPARATOR;
+    if (int rc = ocx_dev_simulate_alg_curve_etas(&L, cx->zt.as<double>(), cx->yt.as<double>(),
+                                                 etas, M, cx->sw.as<int64_t>(), K, o, o + nk,
+                                                 o + 2 * nk, oc, flags, cx->theta.p, (size_t)wsb,
+                                                 st))
+        return rc;
+    std::vector<double> h(3 * nk + (nk + 1) / 2);
+    OCX_HIP(hipMemcpyAsync(h.data(), o, nk * (3 * 8 + 4), hipMemcpyDeviceToHost, st));
+    OCX_HIP(hipStreamSynchronize(st));
+    if (regret) std::memcpy(regret, h.data(), nk * 8);
+    if (cum_loss) std::memcpy(cum_loss, h.data() + nk, nk * 8);
+    if (comp_loss) std::memcpy(comp_loss, h.data() + 2 * nk, nk * 8);
+    if (closed_out) std::memcpy(closed_out, h.data() + 3 * nk, nk * 4);
     return OCX_OK;
 }
 

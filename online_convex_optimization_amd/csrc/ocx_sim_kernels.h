@@ -46,6 +46,22 @@ hipError_t ocx_launch_alg_etas(const ocx_layout* L, const double* zt, const doub
                                const double* etas, int64_t M, double* reg, double* cum,
                                double* comp, int* closed_out, int onepass, int group,
                                hipStream_t st);
+// Regret grids (ocx_alg_curve_etas.hip): FTRL for the M step sizes etas (HOST, read at call
+// time), each observed at the K checkpoints ck (device, strictly increasing in [0, T]), in
+// passes of at most `group` (1, 2 or 4; ocx_grid_instance) step sizes; outputs [B][M][K] (each
+// nullable).  Each pass is followed by the streamed comparator of the triples the closed form
+// (onepass) did not take, from ws (ocx_grid_ws_bytes(L, K, min(group, M)) bytes of device
+// memory, reused by the next pass).  ocx_grid_best_group: the group the measurements chose.
+bool ocx_grid_instance(const ocx_layout* L, int group);
+int ocx_grid_best_group(const ocx_layout* L);
+int64_t ocx_grid_ws_bytes(const ocx_layout* L, int64_t K, int64_t ne);
+hipError_t ocx_launch_alg_grid(const ocx_layout* L, const double* zt, const double* yt,
+                               const double* etas, int64_t M, const int64_t* ck, int64_t K,
+                               double* reg, double* cum, double* comp, int* closed_out,
+                               int onepass, int group, void* ws, hipStream_t st);
+// gmax[n] = max(start, max_b r[b][n]) over r [B][N]; start +0.0, or gmax[n] with accumulate
+hipError_t ocx_launch_max_cols(const double* r, int64_t B, int64_t N, double* gmax,
+                               int accumulate, hipStream_t st);
 // the lean form over wave-groups [g0, g0 + gn) (<= 128 VGPRs; FTRL, 8 x 8 and 16 x 4 layouts),
 // the FTRL side of the overlapped pipeline (ocx_pipeline.hip)
 bool ocx_pipe_lean_supported(const ocx_layout* L);

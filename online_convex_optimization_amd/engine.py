@@ -164,6 +164,38 @@ def simulate_alg_etas_batch(z, y, etas, *, lanes_per_seq: int = LANES_BEST, devi
     return reg
 
 
+def simulate_alg_curve_etas_batch(z, y, checkpoints, etas, *, lanes_per_seq: int = LANES_BEST,
+                                  device: int = 0, return_all: bool = False):
+    """Regret grid: FTRL (fast_algorithms.py:88-115) over B sequences for every eta0 of
+    ``etas``, observed at every horizon of ``checkpoints`` (strictly increasing in [0, T]),
+    each pass over z serving a group of step sizes (ocx_simulate_alg_curve_etas_batch).
+
+    Element (b, m, k) is simulate_alg with eta0 = etas[m] on (z[b, :t_k], y[b, :t_k]), bit for
+    bit in the same layout: [:, m, :] is simulate_alg_curve_batch with etas[m], and with
+    t_K = T, [:, :, -1] is simulate_alg_etas_batch.  Bit-exact modes (lanes_per_seq 1 / -k)
+    stream the reference's comparator sum for every triple; the others take the closed form
+    where the kernel certifies the (sequence, eta, prefix) triple.  Returns regret [B, M, K]
+    or, with ``return_all``, (regret, cum_loss, comp_loss, closed) — closed [B, M, K] int32, 1
+    where the closed form was taken."""
+    z = _f64(z)
+    y = _f64(y)
+    B, T, d = _check_zy(z, y)
+    ck = _checkpoints(checkpoints, T)
+    et = _etas(etas)
+    K, M = int(ck.size), int(et.size)
+    reg = np.zeros((B, M, K))
+    cum = np.zeros((B, M, K)) if return_all else None
+    comp = np.zeros((B, M, K)) if return_all else None
+    closed = np.zeros((B, M, K), dtype=np.int32) if return_all else None
+    _lib.call("ocx_simulate_alg_curve_etas_batch", ptr(z), ptr(y), B, T, d, ptr(et), M,
+              ck.ctypes.data_as(_lib.c_i64p), K, ptr(reg), ptr(cum), ptr(comp),
+              closed.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if return_all else None,
+              int(lanes_per_seq), int(device))
+    if return_all:
+        return reg, cum, comp, closed
+    return reg
+
+
 def simulate_smart_batch(z, y, thresh, eta0: float = SQRT2, *, lanes_per_seq: int = LANES_BEST,
                          device: int = 0, return_switch: bool = False):
     """fast_algorithms.py:118-164 over B sequences; thresh scalar or [B].  Bit-exact modes
@@ -957,6 +989,49 @@ class DeviceBatch:
             self._call("ocx_test_simulate_alg_etas", *args, int(_group), self._sp)
         return out
 
+    def simulate_alg_curve_etas(self, checkpoints, etas,
+                                closed_comparator: Optional[bool] = None, *, _group=None):
+        """Regret grid of the resident batch (ocx_dev_simulate_alg_curve_etas, async): FTRL for
+        every eta0 of ``etas`` (validated as in simulate_alg_etas) observed at every horizon
+        of ``checkpoints`` (validated as in simulate_alg_curve), each pass over z serving
+        ocx_curve_etas_group(L, M) step sizes.  Returns device tensors ``regret``, ``cum``,
+        ``comp`` (float64) and ``closed`` (int32), each [B, M, K]; element (b, m, k) is what
+        simulate_alg(0, etas[m]) gives on the batch truncated at t_k, bit for bit in the same
+        layout — [:, m, :] is simulate_alg_curve(checkpoints, 0, etas[m]) and, with t_K = T,
+        [:, :, -1] is simulate_alg_etas(etas).  ``closed_comparator`` defaults as in
+        simulate_alg; a (sequence, eta, checkpoint) triple the kernel cannot certify streams
+        the comparator pass over its prefix.  (``_group``: tests and tools/grid_probe.py force
+        the group size through include/ocx_testing.h.)"""
+        torch = self.torch
+        ck = _checkpoints(checkpoints, self.L.T)
+        et = _etas(etas)
+        K, M, B = int(ck.size), int(et.size), int(self.L.B)
+        if closed_comparator is None:
+            closed_comparator = not self.exact
+        flags = _lib.OCX_ALG_CLIPPED_ROWS if closed_comparator else 0
+        nbytes = int(_lib.load().ocx_curve_etas_workspace_bytes(self._lp(), K, M))
+        if nbytes < 0:
+            _lib.check(nbytes, "ocx_curve_etas_workspace_bytes")
+        if _group is not None:  # a forced group may hold more columns than the dispatcher's
+            nbytes = max(nbytes, int(self.L.G) * K * min(int(_group), M) * 64
+                         * (8 * int(self.L.C) + 12))
+        with torch.cuda.device(self.device), self._on_stream():
+            ckd = torch.as_tensor(ck).to(self.device)
+            out = {k: torch.zeros((B, M, K), dtype=torch.float64, device=self.device)
+                   for k in ("regret", "cum", "comp")}
+            out["closed"] = torch.zeros((B, M, K), dtype=torch.int32, device=self.device)
+            ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self.device)
+        head = (self._lp(), self.z.data_ptr(), self.y.data_ptr(), ptr(et), M,
+                ckd.data_ptr() if K else None, K, out["regret"].data_ptr(),
+                out["cum"].data_ptr(), out["comp"].data_ptr(), out["closed"].data_ptr(), flags)
+        tail = (ws.data_ptr(), ws.numel() * 8, self._sp)
+        if _group is None:
+            self._call("ocx_dev_simulate_alg_curve_etas", *head, *tail)
+        else:
+            self._call("ocx_test_simulate_alg_curve_etas", *head, int(_group), *tail)
+        self._keep_grid = self._hold(ckd, ws)
+        return out
+
     def simulate_smart(self, thresh, eta0: float = SQRT2, switch_step=None,
                        closed_prefix: Optional[bool] = None,
                        closed_comparator: Optional[bool] = None, stats=None):
@@ -1577,3 +1652,115 @@ def gT_regrets_etas(T: int, runs: int, etas, *, base_seed: int = 0, d: int = 5, 
             out = reg.cpu().numpy()
             cl = closed.cpu().numpy() if closed is not None else None
     return (out, cl) if return_closed else out
+
+
+def _gT_grid_batches(T, runs, ck, et, base_seed, d, run0, lanes_per_seq, device, batch, each):
+    """The batch loop of gT_regret_curves_etas and gT_surface: every batch of the g(T)
+    sampler's sequences generated once (DeviceBatch.generate_gT) and simulated for every step
+    size and horizon (simulate_alg_curve_etas); ``each(db, r0, n, res)`` receives the batch's
+    device results.  ``batch`` None: as many sequences as keep z, y and the grid workspace
+    under GT_CURVE_HBM_BUDGET bytes.  Returns the last DeviceBatch (its stream orders the
+    results)."""
+    K, M = int(ck.size), int(et.size)
+    release_buffers(device)
+    if batch is None:
+        L = _lib.layout(runs, T, d, lanes_per_seq)  # bytes per wave-group of S sequences
+        ne = min(max(int(_lib.load().ocx_curve_etas_group(ctypes.byref(L), M)), 1), M)
+        per_group = 8 * (L.z_elems + L.y_elems) // L.G + 64 * K * ne * (8 * L.C + 12)
+        batch = max(1, GT_CURVE_HBM_BUDGET // max(per_group, 1)) * L.S
+    batch = min(int(batch), runs)
+    db = None
+    for r0 in range(0, runs, batch):
+        n = min(batch, runs - r0)
+        if db is None or db.L.B != n:
+            db = None  # the short last batch: free the full one first
+            db = DeviceBatch(n, T, d, lanes_per_seq=lanes_per_seq, device=int(device))
+        db.generate_gT(base_seed, int(run0) + r0)
+        each(db, r0, n, db.simulate_alg_curve_etas(ck, et))
+    return db
+
+
+def _gT_grid_args(T, runs, checkpoints, etas, base_seed, batch):
+    if base_seed < 0 or base_seed >= 2 ** 64:
+        raise ValueError("base_seed must be in [0, 2**64)")
+    T, runs = int(T), int(runs)
+    if runs < 0:
+        raise ValueError("runs must be >= 0")
+    ck = _checkpoints(checkpoints, T)
+    et = _etas(etas)
+    if batch is not None and int(batch) < 1:
+        raise ValueError("batch must be >= 1")
+    return T, runs, ck, et
+
+
+def gT_regret_curves_etas(T: int, runs: int, checkpoints, etas, *, base_seed: int = 0,
+                          d: int = 5, run0: int = 0, lanes_per_seq: int = LANES_BEST,
+                          device: int = 0, batch: Optional[int] = None,
+                          return_closed: bool = False):
+    """FTRL's regret grid on the g(T) sampler: the sequences _rng(base_seed, T, run), run in
+    [run0, run0 + runs) (fast_algorithms.py:230-241 at horizon T, with a ``d`` parameter), for
+    every eta0 of ``etas`` observed at every horizon of ``checkpoints``.  Returns regret
+    [runs, M, K] (and closed [runs, M, K] int32 with ``return_closed``); [:, m, :] is
+    gT_regret_curves(..., eta0=etas[m]) and, with t_K = T, [:, :, -1] is gT_regrets_etas.
+
+    Each batch is generated once on device and simulated for every step size and horizon
+    (simulate_alg_curve_etas), in batches of ``batch`` sequences — by default as many as keep
+    z, y and the grid workspace under GT_CURVE_HBM_BUDGET bytes; a short last batch is
+    handled.  The library's cached buffers are released first.  Only the [runs, M, K] result
+    crosses PCIe."""
+    import torch
+    T, runs, ck, et = _gT_grid_args(T, runs, checkpoints, etas, base_seed, batch)
+    K, M = int(ck.size), int(et.size)
+    if runs == 0 or K == 0 or M == 0:
+        empty = np.zeros((runs, M, K))
+        return (empty, np.zeros((runs, M, K), dtype=np.int32)) if return_closed else empty
+    dev = torch.device("cuda", int(device))
+    with torch.cuda.device(dev):
+        reg = torch.empty((runs, M, K), dtype=torch.float64, device=dev)
+        closed = (torch.empty((runs, M, K), dtype=torch.int32, device=dev)
+                  if return_closed else None)
+
+        def each(db, r0, n, res):
+            with db._on_stream():
+                reg[r0:r0 + n].copy_(res["regret"])
+                if closed is not None:
+                    closed[r0:r0 + n].copy_(res["closed"])
+
+        db = _gT_grid_batches(T, runs, ck, et, base_seed, d, run0, lanes_per_seq, device, batch,
+                              each)
+        with db._on_stream():
+            out = reg.cpu().numpy()
+            cl = closed.cpu().numpy() if closed is not None else None
+    return (out, cl) if return_closed else out
+
+
+def gT_surface(T: int, runs: int, checkpoints, etas, *, base_seed: int = 0, d: int = 5,
+               run0: int = 0, lanes_per_seq: int = LANES_BEST, device: int = 0,
+               batch: Optional[int] = None):
+    """g[M, K] = max(0, max over runs of gT_regret_curves_etas(...)[:, m, k]): the largest
+    regret of FTRL with eta0 = etas[m] at horizon t_k over the g(T) sampler's runs, reduced on
+    device batch by batch (ocx_dev_max_regret_cols); only M·K doubles cross PCIe.
+
+    What it is: the ANYTIME regret on the longest horizon's rows — every horizon of
+    ``checkpoints`` is read off the same sequences _rng(base_seed, T, run).  It is not the
+    reference's g(T) at T = t_k, which draws a fresh sequence per T (the generator is seeded
+    with the horizon); column K-1 at t_K = T is gT_max(T, runs, eta0=etas[m])."""
+    import torch
+    T, runs, ck, et = _gT_grid_args(T, runs, checkpoints, etas, base_seed, batch)
+    K, M = int(ck.size), int(et.size)
+    if runs == 0 or K == 0 or M == 0:
+        return np.zeros((M, K))
+    dev = torch.device("cuda", int(device))
+    with torch.cuda.device(dev):
+        g = torch.zeros((M, K), dtype=torch.float64, device=dev)
+
+        def each(db, r0, n, res):
+            db._call("ocx_dev_max_regret_cols", res["regret"].data_ptr(), n, M * K,
+                     g.data_ptr(), 1 if r0 else 0, db._sp)
+            db._hold(res["regret"], g)
+
+        db = _gT_grid_batches(T, runs, ck, et, base_seed, d, run0, lanes_per_seq, device, batch,
+                              each)
+        with db._on_stream():
+            out = g.cpu().numpy()
+    return out
