@@ -68,7 +68,8 @@
  * (ocx_twin32_cols_group, ocx_dev_twin32_cols, ocx_twin32_cols_batch), and for the regret-grid
  * symbols (ocx_curve_etas_group, ocx_curve_etas_workspace_bytes,
  * ocx_dev_simulate_alg_curve_etas, ocx_simulate_alg_curve_etas_batch,
- * ocx_dev_max_regret_cols).
+ * ocx_dev_max_regret_cols), and for the SMART regret-grid symbols (ocx_smart_grid_group,
+ * ocx_dev_simulate_smart_grid, ocx_simulate_smart_grid_batch).
  *
  * Checking the ABI: one intermediate 0.1.x tree exported ocx_ftrl_vs_exact_batch WITH a
  * `norm` argument under the same symbol and the same version number as the release without
@@ -733,6 +734,62 @@ int ocx_simulate_smart_curve_batch(const double* z, const double* y, int64_t B, 
                                    int64_t d, const int64_t* horizons, const double* thresh,
                                    int64_t K, double eta0, double* regret, int64_t* switch_step,
                                    int lanes_per_seq, int device);
+
+/* SMART regret grids: SMART (fast_algorithms.py:118-164) for M thresholds, each observed at K
+ * checkpoint horizons 0 <= t_1 < ... < t_K <= T, in passes over z that each serve a group of
+ * thresholds and run once, to t_K.  The surface R(threshold, T) as a pair list
+ * (ocx_dev_simulate_smart_curve over M*K pairs) computes every trajectory K times: a
+ * threshold's column at t_k and at t_{k+1} are the same run.  Here the FTL leg, the prefix loss
+ * of the switch test and the comparator of a checkpoint are formed once per pass; no column
+ * freezes.  Outputs are [B][M][K] row-major, and for every (m, k)
+ *   regret[b][m][k], switch_step[b][m][k]
+ * are bit for bit what ocx_dev_simulate_smart_ex's lane-group kernel gives on
+ * (z[b][:t_k], y[b][:t_k]) with thresh[b] = thresh[b][m], the same layout and the same flags.
+ * So [:, m, :] is ocx_dev_simulate_smart_curve on (t_k, thresh[.][m]) for every k, and with
+ * t_K = T, [:, :, K-1] is ocx_dev_simulate_smart_thresholds.  switch_step[b][m][k] is the full
+ * run's step s where 0 <= s < t_k, else -1; t_k = 0 gives 0.0 and -1; thresh = +inf is FTL's
+ * regret at every horizon.  The result depends neither on the group size nor on a column's
+ * neighbours.  NaN and +-inf thresholds as in the threshold sweep, any order, duplicates
+ * allowed; OCX_SMART_CLOSED_PREFIX and its guard band are unchanged.  The closed comparator
+ * (OCX_ALG_CLOSED_COMPARATOR) is certified per (sequence, checkpoint) by that prefix's steps;
+ * an uncertified pair streams rows 0 .. t_k-1 in place, once for all columns of the pass.  A
+ * pass never looks past t_K and needs no workspace.
+ *
+ * thresholds one pass over z serves in layout L (1: one pass per threshold; negative
+ * ocx_status on error).  Never above the smallest group that holds M; 1 for M <= 1
+ * (DESIGN.md 3.17). */
+int ocx_smart_grid_group(const ocx_layout* L, int64_t M);
+
+/* device: thresh is a DEVICE array [B][M] row-major; checkpoints is a DEVICE int64 array [K],
+ * strictly increasing in [0, T].  It cannot be validated without a synchronisation: a bad
+ * list is the caller's error and gives meaningless numbers, but the kernels never leave the
+ * batch or the outputs, and terminate (a checkpoint is clamped to [0, T]; a segment that
+ * would go backwards is empty).  regret [B][M][K] device, switch_step [B][M][K] int64 device,
+ * nullable.  flags: those of ocx_dev_simulate_smart_ex; unknown flags and NULL arrays are
+ * OCX_E_INVALID before anything is launched.  stats (nullable, device uint64 [2]), per launch
+ * (ceil(M / group) launches): += (sequence, step) pairs that re-scanned (a step re-scans only
+ * while some column of the launch is unswitched and the step is before t_K), += (sequence,
+ * column, checkpoint) triples that took the closed comparator.  M == 0, K == 0, B == 0 and
+ * T == 0 are valid; asynchronous, no allocation, no sync: capture-safe like the other dev
+ * entry points (a replayed graph reads the checkpoints the device array then holds).  With
+ * flags 0 and stats NULL in an exact layout at d <= 64 and B <= 32768 the
+ * one-wave-per-sequence form runs (up to eight columns per prefix re-scan and per comparator
+ * scan; at every M, where the sweeps keep M <= 4 columns on the lane-group kernel above d = 32:
+ * DESIGN.md 3.17): the same bits.  OCX_SMART_KERNEL=lanes|wave is honoured as there. */
+int ocx_dev_simulate_smart_grid(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                                const double* thresh, int64_t M, const int64_t* checkpoints,
+                                int64_t K, double eta0, double* regret, int64_t* switch_step,
+                                int flags, unsigned long long* stats, void* stream);
+
+/* host: numpy buffers in, [B][M][K] out; thresh HOST [B][M], checkpoints HOST [K], whose order
+ * and range, the counts and the NULLs are checked before a device is touched; switch_step
+ * nullable.  Bit-exact layouts (lanes_per_seq 1 / -k): flags 0; other modes: both closed
+ * forms, as ocx_simulate_smart_thresholds_batch. */
+int ocx_simulate_smart_grid_batch(const double* z, const double* y, int64_t B, int64_t T,
+                                  int64_t d, const double* thresh, int64_t M,
+                                  const int64_t* checkpoints, int64_t K, double eta0,
+                                  double* regret, int64_t* switch_step, int lanes_per_seq,
+                                  int device);
 
 /* exact_ftl.py:306-333 on device; a_tiled is the actions [B][T+1][d] tiled with a
  * layout of T+1 steps (z/y use L, actions use La with La->T == L->T + 1). */

@@ -118,6 +118,30 @@ int ocx_test_simulate_smart_wave_cols(const ocx_layout* L, const double* z_tiled
                                       double* regret, int64_t* switch_step,
                                       unsigned long long* stats, int group, void* stream);
 
+/* ocx_dev_simulate_smart_grid on the lane-group kernel (ocx_smart_grid_kernel) with the group
+ * size forced to `group` (1, 2 or 4) instead of the dispatch's choice.  OCX_E_UNSUPPORTED where
+ * that form is not instantiated for the layout (group 2 above 16 coordinates per lane, group 4
+ * above 8).  Asynchronous like the product call. */
+int ocx_test_simulate_smart_grid(const ocx_layout* L, const double* z_tiled,
+                                 const double* y_tiled, const double* thresh, int64_t M,
+                                 const int64_t* checkpoints, int64_t K, double eta0,
+                                 double* regret, int64_t* switch_step, int flags,
+                                 unsigned long long* stats, int group, void* stream);
+
+/* The one-wave-per-sequence form of the SMART grid (ocx_smart_wave_grid_kernel), forced: always
+ * that kernel, in any layout and at any batch size, in launches of `group` (1, 2, 4 or 8)
+ * columns.  Re-scan mode only: flags must be 0.  thresh [B][M], checkpoints [K] int64 and the
+ * outputs [B][M][K] are device arrays as in ocx_dev_simulate_smart_grid.  The kernel adds in the
+ * reference's order whatever the layout.  stats (device [2], nullable): stats[0] += the
+ * (sequence, step) pairs whose switch test ran, once per step however many columns of the
+ * launch needed it; stats[1] is left alone.  OCX_E_UNSUPPORTED for d > 64.  Asynchronous like
+ * the product call. */
+int ocx_test_simulate_smart_wave_grid(const ocx_layout* L, const double* z_tiled,
+                                      const double* y_tiled, const double* thresh, int64_t M,
+                                      const int64_t* checkpoints, int64_t K, double eta0,
+                                      double* regret, int64_t* switch_step, int flags,
+                                      unsigned long long* stats, int group, void* stream);
+
 /* ocx_dev_twin32_cols in launches of `group` (1, 2, 4 or 8) consecutive columns instead of
  * ocx_twin32_cols_group's choice, so a test reaches every instantiated width.
  * OCX_E_UNSUPPORTED where group * C > 64 (group 8 above 8 coordinates, group 4 above 16).

@@ -122,6 +122,11 @@ SIGNATURES = {
                                              c_i64, c_double, c_vp, c_vp, c_int, c_vp, c_vp]),
     "ocx_simulate_smart_curve_batch": (c_int, [c_dp, c_dp, c_i64, c_i64, c_i64, c_i64p, c_dp,
                                                c_i64, c_double, c_dp, c_i64p, c_int, c_int]),
+    "ocx_smart_grid_group": (c_int, [ctypes.POINTER(Layout), c_i64]),
+    "ocx_dev_simulate_smart_grid": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_vp, c_i64, c_vp,
+                                            c_i64, c_double, c_vp, c_vp, c_int, c_vp, c_vp]),
+    "ocx_simulate_smart_grid_batch": (c_int, [c_dp, c_dp, c_i64, c_i64, c_i64, c_dp, c_i64, c_i64p,
+                                              c_i64, c_double, c_dp, c_i64p, c_int, c_int]),
     "ocx_dev_ftrl_vs_exact_ex": (c_int,[ctypes.POINTER(Layout), c_vp, c_vp, c_double, c_vp, c_vp,
                                          c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
     "ocx_ftrl_exact_curve_workspace_bytes": (c_i64, [ctypes.POINTER(Layout), c_i64, c_int]),
@@ -179,6 +184,12 @@ TEST_SIGNATURES = {
     "ocx_test_simulate_smart_wave_cols": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_i64p, c_vp,
                                                   c_i64, c_double, c_vp, c_vp, c_vp, c_int,
                                                   c_vp]),
+    "ocx_test_simulate_smart_grid": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_vp, c_i64, c_vp,
+                                             c_i64, c_double, c_vp, c_vp, c_int, c_vp, c_int,
+                                             c_vp]),
+    "ocx_test_simulate_smart_wave_grid": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_vp, c_i64,
+                                                  c_vp, c_i64, c_double, c_vp, c_vp, c_int, c_vp,
+                                                  c_int, c_vp]),
     "ocx_test_twin32_cols": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_i64, c_i64p, c_i32p,
                                      c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp]),
     "ocx_test_trailing_batches": (c_i64, []),

@@ -16,6 +16,7 @@
 #include "../../include/ocx.h"
 #include "../../include/ocx_testing.h"
 #include "ocx_sim_kernels.h"
+#include "ocx_smart_grid.h"
 
 
 namespace {
@@ -901,6 +902,116 @@ int ocx_test_simulate_smart_wave_cols(const ocx_layout* L, const double* z_tiled
     return OCX_OK;
 }
 
+// the smallest instantiated group that holds M thresholds, capped at `best`
+static int smart_grid_group_for(const ocx_layout* L, int64_t M, int best) {
+    int g = best;
+    while (g > 1 && (g / 2 >= M || !ocx_smart_grid_instance(L, g))) g /= 2;
+    return g;
+}
+
+int ocx_smart_grid_group(const ocx_layout* L, int64_t M) {
+    if (int rc = check_layout(L)) return rc;
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    return smart_grid_group_for(L, M, ocx_smart_grid_best_group(L));
+}
+
+// The grid's one-wave-per-sequence form (ocx_smart_wave_grid.hip) is taken where
+// smart_sweep_takes_wave allows the sweeps' (group unforced, re-scan mode, no stats tensor, an
+// exact layout, ocx_smart_wave_sizes), but without its last condition: the sweeps ask
+// ocx_smart_wave_cols_worth(L, M), which at 32 < d <= 64 keeps M <= 4 columns on the lane-group
+// kernel.  Measured for the grid (profiles/smart_grid_ab.jsonl case x) that
+// choice lost to the pair list, whose M·K columns take the wave form: 2 048 x 1e3 x 64 on one
+// lane, M = 2: 2 972 ms against 427 ms, the wave grid 165 ms; on the 8 x 8 chain the wave grid
+// ties the lane-group grid or wins.  The wave grid does a subset of the wave pair list's work,
+// so it is taken at every size the wave kernels run.  OCX_SMART_KERNEL as for the sweeps.
+static bool smart_grid_takes_wave(const ocx_layout* L, int flags, const void* stats, int group) {
+    if (group != 0 || flags != 0 || stats) return false;
+    if (!(L->chain || L->P == 1)) return false;
+    if (!ocx_smart_wave_sizes(L)) return false;
+    if (const char* e = std::getenv("OCX_SMART_KERNEL")) return std::strcmp(e, "wave") == 0;
+    return true;
+}
+
+// group 0: the dispatcher's choice
+static int dev_simulate_smart_grid(const ocx_layout* L, const double* z_tiled,
+                                   const double* y_tiled, const double* thresh, int64_t M,
+                                   const int64_t* checkpoints, int64_t K, double eta0,
+                                   double* regret, int64_t* switch_step, int flags,
+                                   unsigned long long* stats, int group, void* stream) {
+    StreamDevice sd_(stream);
+    if (int rc = check_layout(L)) return rc;
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    if (flags & ~(OCX_SMART_CLOSED_PREFIX | OCX_ALG_CLOSED_COMPARATOR | OCX_ALG_CLIPPED_ROWS))
+        return fail(OCX_E_INVALID, "unknown flags");
+    if (group != 0 && group != 1 && group != 2 && group != 4)
+        return fail(OCX_E_INVALID, "group must be 1, 2 or 4");
+    if (group != 0 && !ocx_smart_grid_instance(L, group))
+        return fail(OCX_E_UNSUPPORTED, "no group-" + std::to_string(group) + " form at " +
+                                           std::to_string(L->C) + " coordinates per lane");
+    if (M == 0 || K == 0 || L->G == 0) return OCX_OK;
+    if (!thresh || !regret) return fail(OCX_E_INVALID, "NULL thresh/regret");
+    if (!checkpoints) return fail(OCX_E_INVALID, "NULL checkpoints");
+    if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL input buffer");
+    if (smart_grid_takes_wave(L, flags, stats, group)) {
+        OCX_HIP(ocx_launch_smart_wave_grid(L, z_tiled, y_tiled, thresh, M, checkpoints, K, eta0,
+                                           regret, switch_step, nullptr,
+                                           ocx_smart_wave_cols_group(L, M), (hipStream_t)stream));
+        return OCX_OK;
+    }
+    if (group == 0) group = smart_grid_group_for(L, M, ocx_smart_grid_best_group(L));
+    OCX_HIP(ocx_launch_smart_grid(
+        L, z_tiled, y_tiled, thresh, M, checkpoints, K, eta0, regret, switch_step,
+        (flags & OCX_SMART_CLOSED_PREFIX) ? 1 : 0,
+        (flags & (OCX_ALG_CLOSED_COMPARATOR | OCX_ALG_CLIPPED_ROWS)) ? 1 : 0, stats, group,
+        (hipStream_t)stream));
+    return OCX_OK;
+}
+
+int ocx_dev_simulate_smart_grid(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                                const double* thresh, int64_t M, const int64_t* checkpoints,
+                                int64_t K, double eta0, double* regret, int64_t* switch_step,
+                                int flags, unsigned long long* stats, void* stream) {
+    return dev_simulate_smart_grid(L, z_tiled, y_tiled, thresh, M, checkpoints, K, eta0, regret,
+                                   switch_step, flags, stats, 0, stream);
+}
+
+int ocx_test_simulate_smart_grid(const ocx_layout* L, const double* z_tiled,
+                                 const double* y_tiled, const double* thresh, int64_t M,
+                                 const int64_t* checkpoints, int64_t K, double eta0,
+                                 double* regret, int64_t* switch_step, int flags,
+                                 unsigned long long* stats, int group, void* stream) {
+    if (group != 1 && group != 2 && group != 4)
+        return fail(OCX_E_INVALID, "group must be 1, 2 or 4");
+    return dev_simulate_smart_grid(L, z_tiled, y_tiled, thresh, M, checkpoints, K, eta0, regret,
+                                   switch_step, flags, stats, group, stream);
+}
+
+int ocx_test_simulate_smart_wave_grid(const ocx_layout* L, const double* z_tiled,
+                                      const double* y_tiled, const double* thresh, int64_t M,
+                                      const int64_t* checkpoints, int64_t K, double eta0,
+                                      double* regret, int64_t* switch_step, int flags,
+                                      unsigned long long* stats, int group, void* stream) {
+    StreamDevice sd_(stream);
+    if (int rc = check_layout(L)) return rc;
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    if (flags != 0)
+        return fail(OCX_E_INVALID, "the one-wave-per-sequence form is the re-scan mode: flags 0");
+    if (!ocx_smart_wave_grid_instance(group))
+        return fail(OCX_E_INVALID, "group must be 1, 2, 4 or 8");
+    if (L->d > 64)
+        return fail(OCX_E_UNSUPPORTED, "the one-wave-per-sequence form holds d <= 64, got d = " +
+                                           std::to_string(L->d));
+    if (M == 0 || K == 0 || L->B == 0) return OCX_OK;
+    if (!thresh || !regret) return fail(OCX_E_INVALID, "NULL thresh/regret");
+    if (!checkpoints) return fail(OCX_E_INVALID, "NULL checkpoints");
+    if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL input buffer");
+    OCX_HIP(ocx_launch_smart_wave_grid(L, z_tiled, y_tiled, thresh, M, checkpoints, K, eta0,
+                                       regret, switch_step, stats, group, (hipStream_t)stream));
+    return OCX_OK;
+}
+
 int ocx_dev_replay(const ocx_layout* L, const ocx_layout* La, const double* z_tiled,
                    const double* y_tiled, const double* a_tiled, double* cum_loss,
                    double* comp_loss, void* stream) {
@@ -1317,6 +1428,65 @@ int ocx_simulate_smart_curve_batch(const double* z, const double* y, int64_t B, 
     OCX_HIP(hipMemcpyAsync(regret, cx->out.p, nm * 8, hipMemcpyDeviceToHost, st));
     if (switch_step)
         OCX_HIP(hipMemcpyAsync(switch_step, cx->sw.p, nm * 8, hipMemcpyDeviceToHost, st));
+    OCX_HIP(hipStreamSynchronize(st));
+    return OCX_OK;
+}
+
+int ocx_simulate_smart_grid_batch(const double* z, const double* y, int64_t B, int64_t T,
+                                  int64_t d, const double* thresh, int64_t M,
+                                  const int64_t* checkpoints, int64_t K, double eta0,
+                                  double* regret, int64_t* switch_step, int lanes_per_seq,
+                                  int device) {
+    ocx_layout L;
+    if (int rc = ocx_layout_init(B, T, d, lanes_per_seq, &L)) return rc;
+    // everything about the counts and the checkpoints before any device or data pointer is
+    // touched
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    if (K > 0 && !checkpoints) return fail(OCX_E_INVALID, "NULL checkpoints");
+    for (int64_t k = 0; k < K; ++k) {
+        if (checkpoints[k] < 0 || checkpoints[k] > T)
+            return fail(OCX_E_INVALID, "checkpoint " + std::to_string(checkpoints[k]) +
+                                           " outside [0, T = " + std::to_string(T) + "]");
+        if (k > 0 && checkpoints[k] <= checkpoints[k - 1])
+            return fail(OCX_E_INVALID, "checkpoints must be strictly increasing");
+    }
+    if (B == 0 || M == 0 || K == 0) return OCX_OK;
+    if ((T * d > 0 && !z) || (T > 0 && !y) || !thresh || !regret)
+        return fail(OCX_E_INVALID, "NULL argument");
+    DevCtx* cx;
+    if (int rc = ctx_enter(device, &cx)) return rc;
+    std::lock_guard<std::mutex> lk(cx->mu);
+    hipStream_t st = cx->stream;
+    const size_t nz = (size_t)(B * T * d), ny = (size_t)(B * T), nm = (size_t)(B * M),
+                 nk = (size_t)(B * M * K);
+    OCX_HIP(cx->zraw.ensure(nz * 8));
+    OCX_HIP(cx->yraw.ensure(ny * 8));
+    OCX_HIP(cx->zt.ensure((size_t)L.z_elems * 8));
+    OCX_HIP(cx->yt.ensure((size_t)L.y_elems * 8));
+    OCX_HIP(cx->thr.ensure(nm * 8));
+    OCX_HIP(cx->out.ensure(nk * 8));
+    OCX_HIP(cx->sw.ensure(nk * 8));
+    OCX_HIP(cx->theta.ensure((size_t)K * 8));  // the checkpoints
+    if (nz) OCX_HIP(hipMemcpyAsync(cx->zraw.p, z, nz * 8, hipMemcpyHostToDevice, st));
+    if (ny) OCX_HIP(hipMemcpyAsync(cx->yraw.p, y, ny * 8, hipMemcpyHostToDevice, st));
+    OCX_HIP(hipMemcpyAsync(cx->thr.p, thresh, nm * 8, hipMemcpyHostToDevice, st));
+    OCX_HIP(hipMemcpyAsync(cx->theta.p, checkpoints, (size_t)K * 8, hipMemcpyHostToDevice, st));
+    OCX_HIP(ocx_launch_pack(&L, cx->zraw.as<double>(), cx->yraw.as<double>(), cx->zt.as<double>(),
+                            cx->yt.as<double>(), st));
+    // bit-exact modes: the reference's prefix re-scan and streamed comparator; the others:
+    // guarded closed-form prefix, certified closed-form comparator
+    const int flags = (lanes_per_seq == 1 || lanes_per_seq < 0)
+                          ? 0
+                          : (OCX_SMART_CLOSED_PREFIX | OCX_ALG_CLOSED_COMPARATOR);
+    if (int rc = ocx_dev_simulate_smart_grid(&L, cx->zt.as<double>(), cx->yt.as<double>(),
+                                             cx->thr.as<double>(), M, cx->theta.as<int64_t>(), K,
+                                             eta0, cx->out.as<double>(), cx->sw.as<int64_t>(),
+                                             flags, nullptr, st))
+        return rc;
+    OCX_HIP(hipMemcpyAsync(regret, cx->out.p, nk * 8, hipMemcpyDeviceToHost, st));
+    if (switch_step)
+        OCX_HIP(hipMemcpyAsync(switch_step, cx->sw.p, nk * 8, hipMemcpyDeviceToHost, st));
     OCX_HIP(hipStreamSynchronize(st));
     return OCX_OK;
 }

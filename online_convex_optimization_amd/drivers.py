@@ -93,6 +93,42 @@ def case_threshold_regrets(title: str, T: int, thresholds, *, runs: int, replica
             out["switch_step"].cpu().numpy().reshape(runs, replicates, M))
 
 
+def case_threshold_regret_grid(title: str, checkpoints, thresholds, *, runs: int,
+                               replicates: int, base_seed: int = 0, d: int = 5, p: float = 0.10,
+                               block_len: int = 20, lanes_per_seq: int = 1, device: int = 0
+                               ) -> Tuple[np.ndarray, np.ndarray]:
+    """SMART's regret against its switch threshold AND the horizon for one case: (regrets
+    [runs, replicates, M, K], switch_steps [runs, replicates, M, K], -1 = not switched before
+    t_k) for the M values of ``thresholds`` at the K horizons of ``checkpoints`` (strictly
+    increasing), on the batch case_threshold_regrets generates at T = t_K (the same
+    sequences), through one regret grid (DeviceBatch.simulate_smart_grid): every threshold
+    runs once, to t_K, and is read at every checkpoint on the way.
+
+    What the columns are depends on the family.  For the deterministic families (label flips,
+    switching leaders) the prefix of the long sequence IS the reference's sequence at each T,
+    so [..., k] holds case_threshold_regrets(title, t_k, thresholds), bit for bit.  For the
+    random families (i.i.d., Massart) the reference draws a fresh sequence per T
+    (sequence_generation.py:61-62: the generator is seeded with T), so the grid is the anytime
+    regret on the longest horizon's rows — a different sample of the same distribution, not
+    the reference's per-T numbers."""
+    family, stream0 = CASE_FAMILIES[title]
+    grid = np.asarray(checkpoints)
+    ck = engine._checkpoints(grid, int(grid.max()) if grid.size else 0)  # ValueError if bad
+    B, K = runs * replicates, int(ck.size)
+    M = int(engine._thresholds(thresholds, B).shape[1])
+    if B == 0 or K == 0 or M == 0:
+        return (np.zeros((runs, replicates, M, K)),
+                np.full((runs, replicates, M, K), -1, dtype=np.int64))
+    db = engine.DeviceBatch(B, int(ck[-1]), d, lanes_per_seq=lanes_per_seq, device=device)
+    run_idx = np.repeat(np.arange(runs), replicates)
+    rep_idx = np.tile(np.arange(replicates), runs)
+    run_seeds = base_seed + 2025 * (run_idx + 1)  # fast_driver.py:88
+    db.generate_family(family, run_seeds, stream0 + rep_idx, p=p, block_len=block_len)
+    out = db.simulate_smart_grid(ck, thresholds, SQRT2)
+    return (out["regret"][:B].cpu().numpy().reshape(runs, replicates, M, K),
+            out["switch_step"][:B].cpu().numpy().reshape(runs, replicates, M, K))
+
+
 def evaluate_stream_with_stats(title: str, T_grid: Sequence[int], g_emp: Mapping[int, float], *,
                                runs: int = 1, replicates: int = 1, base_seed: int = 0,
                                lanes_per_seq: int = 1, device: int = 0) -> Stats:

@@ -323,6 +323,35 @@ def simulate_smart_curve_batch(z, y, horizons, thresholds=None, eta0: float = SQ
     return (reg, sw) if return_switch else reg
 
 
+def simulate_smart_grid_batch(z, y, checkpoints, thresholds, eta0: float = SQRT2, *,
+                              lanes_per_seq: int = LANES_BEST, device: int = 0,
+                              return_switch: bool = False):
+    """SMART regret grid: SMART (fast_algorithms.py:118-164) over B sequences for every switch
+    threshold of ``thresholds`` ([M], or [B, M] per sequence), observed at every horizon of
+    ``checkpoints`` (strictly increasing in [0, T]); each pass over z serves a group of
+    thresholds and runs once, to the last checkpoint (ocx_simulate_smart_grid_batch).
+
+    Element (b, m, k) is simulate_smart_batch on (z[b, :t_k], y[b, :t_k]) with
+    thresh = thresholds[..., m], bit for bit in the same layout: [:, m, :] is
+    simulate_smart_curve_batch with that threshold at every checkpoint, and with t_K = T,
+    [:, :, -1] is simulate_smart_thresholds_batch.  Bit-exact modes (lanes_per_seq 1 / -k): the
+    reference's prefix re-scan and streamed comparator; the others: both closed forms.
+    Returns regret [B, M, K] or, with ``return_switch``, (regret, switch_step [B, M, K] int64:
+    the full run's switch step where it lies before t_k, else -1)."""
+    z = _f64(z)
+    y = _f64(y)
+    B, T, d = _check_zy(z, y)
+    ck = _checkpoints(checkpoints, T)
+    th = _thresholds(thresholds, B)
+    K, M = int(ck.size), int(th.shape[1])
+    reg = np.zeros((B, M, K))
+    sw = np.full((B, M, K), -1, dtype=np.int64)
+    _lib.call("ocx_simulate_smart_grid_batch", ptr(z), ptr(y), B, T, d, ptr(th), M,
+              ck.ctypes.data_as(_lib.c_i64p), K, float(eta0), ptr(reg),
+              sw.ctypes.data_as(_lib.c_i64p), int(lanes_per_seq), int(device))
+    return (reg, sw) if return_switch else reg
+
+
 def replay_batch(z, y, actions, *, device: int = 0):
     """exact_ftl.py:306-333 over B sequences: actions [B, T+1, d] → (cum_loss, comp_loss)."""
     z = _f64(z)
@@ -1165,6 +1194,65 @@ class DeviceBatch:
         self._keep_th = self._hold(th)
         return out
 
+    def simulate_smart_grid(self, checkpoints, thresholds, eta0: float = SQRT2, *,
+                            closed_prefix: Optional[bool] = None,
+                            closed_comparator: Optional[bool] = None, stats=None,
+                            _group=None, _wave=None):
+        """SMART regret grid of the resident batch (ocx_dev_simulate_smart_grid, async): SMART
+        for every switch threshold of ``thresholds`` ([M], or [B, M] per sequence; validated
+        through _thresholds, NaN and ±inf are legal) observed at every horizon of
+        ``checkpoints`` (strictly increasing in [0, T]; validated through _checkpoints), each
+        pass over z serving ocx_smart_grid_group(L, M) thresholds and running once, to t_K.
+        In a bit-exact layout, in the re-scan mode (both flags off) without ``stats``, at
+        d <= 64 and B <= 32768 the one-wave-per-sequence kernel runs (the same bits).
+        Returns device tensors ``regret`` [B, M, K] float64 and ``switch_step`` [B, M, K] int64
+        (the full run's switch step where it lies before t_k, else -1); element (b, m, k) is
+        what simulate_smart(thresholds[..., m], eta0, stats=...) gives on a batch of the first
+        t_k rows, bit for bit in the same layout — [:, m, :] is simulate_smart_curve with that
+        threshold at every checkpoint and, with t_K = T, [:, :, -1] is
+        simulate_smart_thresholds.  ``closed_prefix`` / ``closed_comparator`` default as in
+        simulate_smart; the closed comparator is certified per (sequence, checkpoint).
+        ``stats`` ([2] int64 device tensor, optional) accumulates, per pass, the (sequence,
+        step) pairs that re-scanned and the (sequence, column, checkpoint) triples that took
+        the closed comparator.  (``_group``: tests and tools/smart_grid_probe.py force the
+        lane-group kernel's group size through include/ocx_testing.h; ``_wave``: they force the
+        one-wave-per-sequence kernel with that group size, 1, 2, 4 or 8, in any layout —
+        re-scan mode only.)"""
+        torch = self.torch
+        B = int(self.L.B)
+        ck = _checkpoints(checkpoints, self.L.T)
+        tha = _thresholds(thresholds, B)
+        K, M = int(ck.size), int(tha.shape[1])
+        if _wave is not None and (closed_prefix or closed_comparator or _group is not None):
+            raise ValueError("_wave runs the re-scan mode only, and excludes _group")
+        if closed_prefix is None:
+            closed_prefix = not self.exact
+        if closed_comparator is None:
+            closed_comparator = not self.exact
+        flags = ((_lib.OCX_SMART_CLOSED_PREFIX if closed_prefix else 0) |
+                 (_lib.OCX_ALG_CLOSED_COMPARATOR if closed_comparator else 0))
+        n = B * M * K
+        with torch.cuda.device(self.device), self._on_stream():
+            th = torch.as_tensor(tha).to(self.device)
+            ckd = torch.as_tensor(ck).to(self.device)
+            out = {"regret": torch.zeros((B, M, K), dtype=torch.float64, device=self.device),
+                   "switch_step": torch.full((B, M, K), -1, dtype=torch.int64,
+                                             device=self.device)}
+        args = (self._lp(), self.z.data_ptr(), self.y.data_ptr(), th.data_ptr() if B * M else None,
+                M, ckd.data_ptr() if K else None, K, float(eta0),
+                out["regret"].data_ptr() if n else None,
+                out["switch_step"].data_ptr() if n else None,
+                0 if _wave is not None else flags,
+                stats.data_ptr() if stats is not None else None)
+        if _wave is not None:
+            self._call("ocx_test_simulate_smart_wave_grid", *args, int(_wave), self._sp)
+        elif _group is None:
+            self._call("ocx_dev_simulate_smart_grid", *args, self._sp)
+        else:
+            self._call("ocx_test_simulate_smart_grid", *args, int(_group), self._sp)
+        self._keep_sgrid = self._hold(th, ckd)
+        return out
+
     def comparison_curves(self, checkpoints, g_emp=None, eta0: float = SQRT2):
         """The four lines of the reference's comparison figure (fast_driver.py:71-127) against
         the horizon, from this resident batch: a dict of [B, K] device tensors ``FTRL``,
@@ -1764,3 +1852,68 @@ def gT_surface(T: int, runs: int, checkpoints, etas, *, base_seed: int = 0, d: i
         with db._on_stream():
             out = g.cpu().numpy()
     return out
+
+
+def gT_smart_grids(T: int, runs: int, checkpoints, thresholds, *, base_seed: int = 0,
+                   d: int = 5, eta0: float = SQRT2, run0: int = 0,
+                   lanes_per_seq: int = LANES_BEST, device: int = 0,
+                   batch: Optional[int] = None, return_switch: bool = False):
+    """SMART's regret grid on the g(T) sampler: the sequences _rng(base_seed, T, run), run in
+    [run0, run0 + runs) (fast_algorithms.py:230-241 at horizon T, with a ``d`` parameter), for
+    every switch threshold of ``thresholds`` ([M]: every run the same) observed at every
+    horizon of ``checkpoints``.  Returns regret [runs, M, K] (and switch_step [runs, M, K]
+    int64 with ``return_switch``); [:, m, :] is SMART with thresholds[m] on the first t_k rows
+    of every run.
+
+    What it is: the ANYTIME regret on the longest horizon's rows — every horizon of
+    ``checkpoints`` is read off the same sequences.  It is not SMART on the reference's g(T)
+    sequences at T = t_k, which are drawn afresh per T.
+
+    Each batch is generated once on device (DeviceBatch.generate_gT) and simulated for every
+    threshold and horizon (simulate_smart_grid), in batches of ``batch`` sequences — by
+    default as many as keep z and y under GT_CURVE_HBM_BUDGET bytes; a short last batch is
+    handled.  The library's cached buffers are released first.  The result does not depend on
+    ``batch``.  Only the [runs, M, K] results cross PCIe."""
+    import torch
+    if base_seed < 0 or base_seed >= 2 ** 64:
+        raise ValueError("base_seed must be in [0, 2**64)")
+    T, runs = int(T), int(runs)
+    if runs < 0:
+        raise ValueError("runs must be >= 0")
+    ck = _checkpoints(checkpoints, T)
+    th = np.asarray(_thresholds(thresholds, 1))
+    if np.asarray(thresholds).ndim != 1:
+        raise ValueError("thresholds must be [M]: one list for every run")
+    th = th[0]
+    if batch is not None and int(batch) < 1:
+        raise ValueError("batch must be >= 1")
+    K, M = int(ck.size), int(th.size)
+    if runs == 0 or K == 0 or M == 0:
+        empty = np.zeros((runs, M, K))
+        return (empty, np.full((runs, M, K), -1, dtype=np.int64)) if return_switch else empty
+    release_buffers(device)
+    if batch is None:
+        L = _lib.layout(runs, T, d, lanes_per_seq)  # bytes per wave-group of S sequences
+        per_group = 8 * (L.z_elems + L.y_elems) // L.G
+        batch = max(1, GT_CURVE_HBM_BUDGET // max(per_group, 1)) * L.S
+    batch = min(int(batch), runs)
+    dev = torch.device("cuda", int(device))
+    with torch.cuda.device(dev):
+        reg = torch.empty((runs, M, K), dtype=torch.float64, device=dev)
+        sw = torch.empty((runs, M, K), dtype=torch.int64, device=dev) if return_switch else None
+        db = None
+        for r0 in range(0, runs, batch):
+            n = min(batch, runs - r0)
+            if db is None or db.L.B != n:
+                db = None  # the short last batch: free the full one first
+                db = DeviceBatch(n, T, d, lanes_per_seq=lanes_per_seq, device=int(device))
+            db.generate_gT(base_seed, int(run0) + r0)
+            res = db.simulate_smart_grid(ck, th, eta0)
+            with db._on_stream():
+                reg[r0:r0 + n].copy_(res["regret"])
+                if sw is not None:
+                    sw[r0:r0 + n].copy_(res["switch_step"])
+        with db._on_stream():
+            out = reg.cpu().numpy()
+            so = sw.cpu().numpy() if sw is not None else None
+    return (out, so) if return_switch else out
