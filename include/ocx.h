@@ -69,7 +69,9 @@
  * symbols (ocx_curve_etas_group, ocx_curve_etas_workspace_bytes,
  * ocx_dev_simulate_alg_curve_etas, ocx_simulate_alg_curve_etas_batch,
  * ocx_dev_max_regret_cols), and for the SMART regret-grid symbols (ocx_smart_grid_group,
- * ocx_dev_simulate_smart_grid, ocx_simulate_smart_grid_batch).
+ * ocx_dev_simulate_smart_grid, ocx_simulate_smart_grid_batch), and for the FTRL-vs-exact-FTL
+ * regret-grid symbols (ocx_ftrl_exact_grid_group, ocx_ftrl_exact_grid_workspace_bytes,
+ * ocx_dev_ftrl_vs_exact_curve_etas, ocx_ftrl_vs_exact_curve_etas_batch).
  *
  * Checking the ABI: one intermediate 0.1.x tree exported ocx_ftrl_vs_exact_batch WITH a
  * `norm` argument under the same symbol and the same version number as the release without
@@ -620,6 +622,58 @@ int ocx_ftrl_vs_exact_curve_batch(const double* z, const double* y, int64_t B, i
                                   double* cum_ftrl, double* cum_exact, double* comp_exact,
                                   double* comp_ftl, double* cmp_action, int32_t* regime,
                                   int32_t* closed, int norm, int lanes_per_seq, int device);
+
+/* FTRL-vs-exact-FTL regret grids: ocx_dev_ftrl_vs_exact_curve for M step sizes per read of z.
+ * Of the two loops only FTRL depends on eta0, so one pass holds NE FTRL columns beside one
+ * exact-FTL column.  For step sizes etas[0..M) (any reals, any order, duplicates allowed) and
+ * checkpoints 0 <= t_1 < ... < t_K <= T,
+ *   cum_ftrl[b][m][k], comp_ftl[b][m][k]                                        ([B][M][K])
+ *   cum_exact[b][k], comp_exact[b][k], regime[b][k], closed[b][k], cmp_action[b][k][:]
+ * carry the bits of ocx_dev_ftrl_vs_exact_curve(eta0 = etas[m]) at column k, with the same
+ * layout, norm and flags — that is, of ocx_dev_ftrl_vs_exact_ex on the batch truncated at t_k.
+ * The second line does not depend on eta0 and is written once.  A plain step-size sweep is the
+ * grid with checkpoints = [T].
+ *
+ * step sizes one pass over z serves in layout L: 1, 2 or 4; negative ocx_status on a bad layout */
+int ocx_ftrl_exact_grid_group(const ocx_layout* L);
+
+/* bytes of caller-owned device workspace for M step sizes and K checkpoints in layout L, enough
+ * for every `group` the layout offers; 0 for M == 0, K == 0 or an empty batch; negative
+ * ocx_status on error (bad layout, M < 0, K < 0, K > T + 1) */
+int64_t ocx_ftrl_exact_grid_workspace_bytes(const ocx_layout* L, int64_t M, int64_t K,
+                                            int with_comp_ftl);
+
+/* device: etas is a HOST array [M], read before the call returns; checkpoints a DEVICE int64
+ * array [K] under ocx_dev_ftrl_vs_exact_curve's precondition and guarantee (whatever it holds,
+ * the kernels never leave the batch, the outputs and the workspace);
+ * cum_ftrl: device [B][M][K] row-major, required; comp_ftl [B][M][K] nullable; cum_exact /
+ * comp_exact [B][K] and regime [B][K] int32 required; cmp_action [B][K][d] and closed [B][K]
+ * int32 nullable; norm, flags: as in ocx_dev_ftrl_vs_exact_curve;
+ * group: step sizes per pass, 0 = ocx_ftrl_exact_grid_group(L) (capped at what M needs), or 1,
+ * 2, 4 where the layout has that instance (OCX_E_UNSUPPORTED otherwise).  With M above the
+ * group the call runs ceil(M / group) passes; every pass re-runs the exact side, the first
+ * writes its outputs.  The results do not depend on the group;
+ * workspace: workspace_bytes >= ocx_ftrl_exact_grid_workspace_bytes(L, M, K, comp_ftl != NULL),
+ * 8-byte aligned, the call's own until the stream has passed it;
+ * M == 0, K == 0 and B == 0 launch nothing; asynchronous, no allocation, no sync. */
+int ocx_dev_ftrl_vs_exact_curve_etas(const ocx_layout* L, const double* z_tiled,
+                                     const double* y_tiled, const double* etas, int64_t M,
+                                     const int64_t* checkpoints, int64_t K, double* cum_ftrl,
+                                     double* cum_exact, double* comp_exact, double* comp_ftl,
+                                     double* cmp_action, int32_t* regime, int32_t* closed,
+                                     int norm, int flags, int group, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+
+/* host: numpy buffers in; cum_ftrl / comp_ftl [B][M][K], the others [B][K] (cmp_action
+ * [B][K][d]) out; etas and checkpoints are HOST arrays, validated here (order, range, M >= 0,
+ * K >= 0) before any device is touched.  lanes_per_seq chooses the closed form and the butterfly
+ * sums as ocx_ftrl_vs_exact_curve_batch does. */
+int ocx_ftrl_vs_exact_curve_etas_batch(const double* z, const double* y, int64_t B, int64_t T,
+                                       int64_t d, const double* etas, int64_t M,
+                                       const int64_t* checkpoints, int64_t K, double* cum_ftrl,
+                                       double* cum_exact, double* comp_exact, double* comp_ftl,
+                                       double* cmp_action, int32_t* regime, int32_t* closed,
+                                       int norm, int lanes_per_seq, int device);
 
 /* fast_algorithms.py:118-164 on device; thresh [B] device. */
 int ocx_dev_simulate_smart(const ocx_layout* L, const double* z_tiled, const double* y_tiled,

@@ -138,6 +138,17 @@ SIGNATURES = {
                                               ctypes.POINTER(ctypes.c_int32),
                                               ctypes.POINTER(ctypes.c_int32), c_int, c_int,
                                               c_int]),
+    "ocx_ftrl_exact_grid_group": (c_int, [ctypes.POINTER(Layout)]),
+    "ocx_ftrl_exact_grid_workspace_bytes": (c_i64, [ctypes.POINTER(Layout), c_i64, c_i64, c_int]),
+    "ocx_dev_ftrl_vs_exact_curve_etas": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_dp, c_i64,
+                                                 c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                 c_vp, c_int, c_int, c_int, c_vp, ctypes.c_size_t,
+                                                 c_vp]),
+    "ocx_ftrl_vs_exact_curve_etas_batch": (c_int, [c_dp, c_dp, c_i64, c_i64, c_i64, c_dp, c_i64,
+                                                   c_i64p, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp,
+                                                   ctypes.POINTER(ctypes.c_int32),
+                                                   ctypes.POINTER(ctypes.c_int32), c_int, c_int,
+                                                   c_int]),
     "ocx_gT_sweep": (c_int, [c_i64p, c_int, c_i64, c_u64, c_i64, c_double, c_int, c_dp, c_dp]),
     "ocx_gT_sweep_devices": (c_int, [c_i64p, c_int, c_i64, c_u64, c_i64, c_double,
                                      ctypes.POINTER(c_int), c_int, c_int, c_dp, c_dp]),

@@ -682,6 +682,82 @@ int ocx_dev_ftrl_vs_exact_curve(const ocx_layout* L, const double* z_tiled, cons
     return OCX_OK;
 }
 
+// the smallest instantiated group of the FTRL-vs-exact grid that holds M step sizes, capped at
+// `best`
+static int fe_grid_group_for(const ocx_layout* L, int64_t M, int best) {
+    int g = best;
+    while (g > 1 && (g / 2 >= M || !ocx_ftrl_exact_grid_instance(L, g))) g /= 2;
+    return g;
+}
+
+// the largest group the layout has an instance for (what a caller may force)
+static int fe_grid_max_group(const ocx_layout* L) {
+    return ocx_ftrl_exact_grid_instance(L, 4) ? 4 : (ocx_ftrl_exact_grid_instance(L, 2) ? 2 : 1);
+}
+
+int ocx_ftrl_exact_grid_group(const ocx_layout* L) {
+    if (int rc = check_layout(L)) return rc;
+    return ocx_ftrl_exact_grid_best_group(L);
+}
+
+int64_t ocx_ftrl_exact_grid_workspace_bytes(const ocx_layout* L, int64_t M, int64_t K,
+                                            int with_comp_ftl) {
+    if (int rc = check_layout(L)) return rc;
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    if (L->B < 0 || L->T < 0 || L->G != ceil_div(L->B, L->S))
+        return fail(OCX_E_INVALID, "corrupt layout");
+    // strictly increasing checkpoints in [0, T]: at most T + 1 of them (bounds the product)
+    if (K > L->T + 1) return fail(OCX_E_INVALID, "more checkpoints than horizons 0..T");
+    if (M == 0) return 0;
+    const int64_t g = fe_grid_max_group(L);
+    return ocx_ftrl_exact_grid_ws_bytes(L, K, M < g ? M : g, with_comp_ftl != 0 ? 1 : 0);
+}
+
+int ocx_dev_ftrl_vs_exact_curve_etas(const ocx_layout* L, const double* z_tiled,
+                                     const double* y_tiled, const double* etas, int64_t M,
+                                     const int64_t* checkpoints, int64_t K, double* cum_ftrl,
+                                     double* cum_exact, double* comp_exact, double* comp_ftl,
+                                     double* cmp_action, int32_t* regime, int32_t* closed,
+                                     int norm, int flags, int group, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    StreamDevice sd_(stream);
+    if (norm < 0 || norm > 2) return fail(OCX_E_INVALID, "norm must be 0 (l2), 1 (l1) or 2 (linf)");
+    // checks the layout, M and K
+    const int64_t need = ocx_ftrl_exact_grid_workspace_bytes(L, M, K, comp_ftl != nullptr);
+    if (need < 0) return (int)need;
+    if (group != 0 && group != 1 && group != 2 && group != 4)
+        return fail(OCX_E_INVALID, "group must be 0, 1, 2 or 4");
+    if (group != 0 && !ocx_ftrl_exact_grid_instance(L, group))
+        return fail(OCX_E_UNSUPPORTED, "no group-" + std::to_string(group) + " form at " +
+                                           std::to_string(L->C) + " coordinates per lane");
+    if (flags & ~(OCX_ALG_CLIPPED_ROWS | OCX_ALG_CLOSED_COMPARATOR | OCX_ALG_TREE_SUMS))
+        return fail(OCX_E_INVALID, "unknown flags");
+    if (M > 0 && !etas) return fail(OCX_E_INVALID, "NULL etas");
+    if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL input buffer");
+    if (K > 0 && !checkpoints) return fail(OCX_E_INVALID, "NULL checkpoints");
+    if (M > 0 && K > 0 && L->B && (!cum_ftrl || !cum_exact || !comp_exact || !regime))
+        return fail(OCX_E_INVALID, "NULL output buffer");
+    if (need > 0 && (!workspace || workspace_bytes < (size_t)need))
+        return fail(OCX_E_INVALID,
+                    "workspace smaller than ocx_ftrl_exact_grid_workspace_bytes(L, M, K, comp_ftl) = " +
+                        std::to_string(need));
+    if (need > 0 && (reinterpret_cast<uintptr_t>(workspace) & 7) != 0)
+        return fail(OCX_E_INVALID, "workspace is not 8-byte aligned");
+    if (M == 0 || K == 0 || L->B == 0) return OCX_OK;
+    if (group == 0) group = fe_grid_group_for(L, M, ocx_ftrl_exact_grid_best_group(L));
+    ocx_layout Lt = *L;
+    if (flags & OCX_ALG_TREE_SUMS) Lt.chain = 0;  // same tiling, butterfly sums
+    if (!ocx_ftrl_exact_grid_instance(&Lt, group))  // (the instance set does not depend on it)
+        return fail(OCX_E_UNSUPPORTED, "no group-" + std::to_string(group) + " form");
+    OCX_HIP(ocx_launch_ftrl_exact_grid(
+        &Lt, z_tiled, y_tiled, etas, M, checkpoints, K, cum_ftrl, cum_exact, comp_exact, comp_ftl,
+        cmp_action, regime, closed,
+        (flags & (OCX_ALG_CLIPPED_ROWS | OCX_ALG_CLOSED_COMPARATOR)) ? 1 : 0, norm, group,
+        workspace, (hipStream_t)stream));
+    return OCX_OK;
+}
+
 int ocx_dev_simulate_smart(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
                            const double* thresh, double eta0, double* regret,
                            int64_t* switch_step, void* stream) {
@@ -1674,6 +1750,79 @@ int ocx_ftrl_vs_exact_curve_batch(const double* z, const double* y, int64_t B, i
     if (comp_ftl) std::memcpy(comp_ftl, h.data() + 3 * nk, nk * 8);
     if (cmp_action && d) std::memcpy(cmp_action, h.data() + 4 * nk, nk * (size_t)d * 8);
     const double* hi = h.data() + nk * (size_t)(4 + d);
+    std::memcpy(regime, hi, nk * 4);
+    if (closed) std::memcpy(closed, reinterpret_cast<const char*>(hi) + nk * 4, nk * 4);
+    return OCX_OK;
+}
+
+int ocx_ftrl_vs_exact_curve_etas_batch(const double* z, const double* y, int64_t B, int64_t T,
+                                       int64_t d, const double* etas, int64_t M,
+                                       const int64_t* checkpoints, int64_t K, double* cum_ftrl,
+                                       double* cum_exact, double* comp_exact, double* comp_ftl,
+                                       double* cmp_action, int32_t* regime, int32_t* closed,
+                                       int norm, int lanes_per_seq, int device) {
+    ocx_layout L;
+    if (int rc = ocx_layout_init(B, T, d, lanes_per_seq, &L)) return rc;
+    if (norm < 0 || norm > 2) return fail(OCX_E_INVALID, "norm must be 0 (l2), 1 (l1) or 2 (linf)");
+    // everything about the step sizes and checkpoints before any device or data pointer is touched
+    if (M < 0) return fail(OCX_E_INVALID, "M < 0");
+    if (M > 0 && !etas) return fail(OCX_E_INVALID, "NULL etas");
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    if (K > 0 && !checkpoints) return fail(OCX_E_INVALID, "NULL checkpoints");
+    for (int64_t k = 0; k < K; ++k) {
+        if (checkpoints[k] < 0 || checkpoints[k] > T)
+            return fail(OCX_E_INVALID, "checkpoint " + std::to_string(checkpoints[k]) +
+                                           " outside [0, T = " + std::to_string(T) + "]");
+        if (k > 0 && checkpoints[k] <= checkpoints[k - 1])
+            return fail(OCX_E_INVALID, "checkpoints must be strictly increasing");
+    }
+    if (B == 0 || K == 0 || M == 0) return OCX_OK;
+    if ((T * d > 0 && !z) || (T > 0 && !y) || !cum_ftrl || !cum_exact || !comp_exact || !regime)
+        return fail(OCX_E_INVALID, "NULL argument");
+    const int64_t wsb = ocx_ftrl_exact_grid_workspace_bytes(&L, M, K, comp_ftl != nullptr);
+    if (wsb < 0) return (int)wsb;
+    DevCtx* cx;
+    if (int rc = ctx_enter(device, &cx)) return rc;
+    std::lock_guard<std::mutex> lk(cx->mu);
+    hipStream_t st = cx->stream;
+    const size_t nz = (size_t)(B * T * d), ny = (size_t)(B * T), nk = (size_t)(B * K);
+    const size_t nmk = nk * (size_t)M;
+    OCX_HIP(cx->zraw.ensure(nz * 8));
+    OCX_HIP(cx->yraw.ensure(ny * 8));
+    OCX_HIP(cx->zt.ensure((size_t)L.z_elems * 8));
+    OCX_HIP(cx->yt.ensure((size_t)L.y_elems * 8));
+    // cum_ftrl, comp_ftl [B][M][K]; cum_exact, comp_exact [B][K]; actions [B][K][d]; regime,
+    // closed int32 [B][K]
+    const size_t nd = 2 * nmk + nk * (size_t)(2 + d);
+    OCX_HIP(cx->out.ensure(nd * 8 + nk * 2 * 4));
+    OCX_HIP(cx->sw.ensure((size_t)K * 8));
+    OCX_HIP(cx->theta.ensure((size_t)wsb));
+    if (nz) OCX_HIP(hipMemcpyAsync(cx->zraw.p, z, nz * 8, hipMemcpyHostToDevice, st));
+    if (ny) OCX_HIP(hipMemcpyAsync(cx->yraw.p, y, ny * 8, hipMemcpyHostToDevice, st));
+    OCX_HIP(hipMemcpyAsync(cx->sw.p, checkpoints, (size_t)K * 8, hipMemcpyHostToDevice, st));
+    OCX_HIP(ocx_launch_pack(&L, cx->zraw.as<double>(), cx->yraw.as<double>(), cx->zt.as<double>(),
+                            cx->yt.as<double>(), st));
+    double* o = cx->out.as<double>();
+    double* oe = o + 2 * nmk;
+    int* rg = reinterpret_cast<int*>(o + nd);
+    // the closed form and the butterfly sums as in ocx_ftrl_vs_exact_curve_batch
+    const int onepass = (lanes_per_seq == 1 || lanes_per_seq < 0) ? 0 : 1;
+    if (lanes_per_seq == OCX_LANES_BEST) L.chain = 0;
+    const int group = fe_grid_group_for(&L, M, ocx_ftrl_exact_grid_best_group(&L));
+    OCX_HIP(ocx_launch_ftrl_exact_grid(&L, cx->zt.as<double>(), cx->yt.as<double>(), etas, M,
+                                       cx->sw.as<int64_t>(), K, o, oe, oe + nk,
+                                       comp_ftl ? o + nmk : nullptr, oe + 2 * nk, rg, rg + nk,
+                                       onepass, norm, group, cx->theta.p, st));
+    std::vector<double> h(nd + nk);
+    OCX_HIP(hipMemcpyAsync(h.data(), o, nd * 8 + nk * 2 * 4, hipMemcpyDeviceToHost, st));
+    OCX_HIP(hipStreamSynchronize(st));
+    std::memcpy(cum_ftrl, h.data(), nmk * 8);
+    if (comp_ftl) std::memcpy(comp_ftl, h.data() + nmk, nmk * 8);
+    const double* he = h.data() + 2 * nmk;
+    std::memcpy(cum_exact, he, nk * 8);
+    std::memcpy(comp_exact, he + nk, nk * 8);
+    if (cmp_action && d) std::memcpy(cmp_action, he + 2 * nk, nk * (size_t)d * 8);
+    const double* hi = h.data() + nd;
     std::memcpy(regime, hi, nk * 4);
     if (closed) std::memcpy(closed, reinterpret_cast<const char*>(hi) + nk * 4, nk * 4);
     return OCX_OK;

@@ -117,3 +117,90 @@ __device__ __forceinline__ void ocx_ftrl_exact_step(double (&tr)[C], double (&te
         te[j] += (-yv) * zj;
     }
 }
+
+// ocx_ftrl_scale's table for NE step sizes: one base, the √ shared, −(η_m/√t) per column — the
+// same expression per (t, m) as OcxScaleTable's, so bit for bit the same scale.
+template <int NE>
+struct OcxScaleCols {
+    double v[NE];
+    int64_t base = INT64_MIN / 2;  // 1-based step of lane 0's entries (none yet)
+};
+
+// Column form of ocx_ftrl_exact_step (the regret grid's step, ocx_ftrl_exact_grid.hip): NE FTRL
+// columns, θ_r^m (tr[m]) at step size eta[m] with its own loss cr[m], beside ONE exact-FTL
+// column.  Formed once: the exact action, its q, ‖θ_e‖², ‖z_t‖², the dual-ball and touch tests,
+// the θ_e update, `linear` and `clipped`.  Formed per column: the scale, the action, ‖x_r‖²,
+// z·x_r, the rescale branch (each column's own test), the loss, the sub-gradient and the θ_r
+// update.  Every total is accumulated on its own (ocx_totals), so the 2 + 2·NE wide call keeps
+// each one's order, and each column's products and sums are those of the NE = 1 step.
+template <int C, int P, bool CHAIN, int NE>
+__device__ __forceinline__ void ocx_ftrl_exact_step_cols(
+    double (&tr)[NE][C], double (&te)[C], const ocx_d2* z, const double& yv, OcxScaleCols<NE>& sct,
+    const int64_t& t, const double (&eta)[NE], const int& norm, double (&cr)[NE], double& ce,
+    bool& linear, bool& clipped, uint64_t& touch, const int& lane) {
+    const int64_t t1 = t + 1;
+    if (t1 - sct.base >= 64 || t1 < sct.base) {
+        sct.base = t1;
+        const double r = sqrt((double)(t1 + lane));
+#pragma unroll
+        for (int m = 0; m < NE; ++m) sct.v[m] = -(eta[m] / r);
+    }
+    double xr[NE][C];
+#pragma unroll
+    for (int m = 0; m < NE; ++m) {
+        const double sc = ocx_readlane(sct.v[m], (int)(t1 - sct.base));
+#pragma unroll
+        for (int j = 0; j < C; ++j) xr[m][j] = sc * tr[m][j];
+    }
+    // totals 2m: ‖x_r^m‖², 2m + 1: z·x_r^m; then ‖θ_e‖² and ‖z_t‖²
+    double tot[2 * NE + 2];
+    ocx_totals<C, P, CHAIN, 2 * NE + 2>(
+        [&](int j, int k) -> double {
+            const double zj = ocx_zj(z, j);
+            if (k == 2 * NE) return te[j] * te[j];
+            if (k == 2 * NE + 1) return zj * zj;
+            const int m = k >> 1;
+            return (k & 1) ? zj * xr[m][j] : xr[m][j] * xr[m][j];
+        },
+        tot, lane);
+    const double te2 = tot[2 * NE], z2 = tot[2 * NE + 1];
+    double qr[NE];
+#pragma unroll
+    for (int m = 0; m < NE; ++m) {
+        qr[m] = tot[2 * m + 1];
+        if (tot[2 * m] > 1.0) {  // FTRL rescale (rare), this column's own test
+            const double f = 1.0 / sqrt(tot[2 * m]);
+#pragma unroll
+            for (int j = 0; j < C; ++j) xr[m][j] *= f;
+            qr[m] = ocx_zdot<C, P, CHAIN>(z, xr[m], lane);
+        }
+    }
+    double xe[C];
+    if (norm == 0) {
+        const double sce = -(1.0 / sqrt(te2));
+#pragma unroll
+        for (int j = 0; j < C; ++j) xe[j] = (te2 == 0.0) ? 0.0 : sce * te[j];
+    } else {
+        ocx_action_exact_poly<C, P>(te, xe, norm, lane);
+        linear = linear && !ocx_exact_poly_tie<C, P>(te, touch, norm);
+    }
+    const double qe = ocx_zdot<C, P, CHAIN>(z, xe, lane);
+    ce += 0.5 * fabs(qe - yv);
+    if (norm == 0) {
+        linear = linear && z2 <= 1.0 + 1e-6 && fabs(yv) == 1.0;
+    } else {
+        linear = linear && ocx_dual_ok<C, P, CHAIN>(z, norm, lane) && fabs(yv) == 1.0;
+        if (norm == 2) touch = ocx_touch<C>(touch, z);
+    }
+    clipped = clipped && z2 <= 1.0 + 1e-12;
+#pragma unroll
+    for (int m = 0; m < NE; ++m) {
+        const double dr = qr[m] - yv;
+        cr[m] += 0.5 * fabs(dr);
+        const double gr = ocx_grad(dr);
+#pragma unroll
+        for (int j = 0; j < C; ++j) tr[m][j] += gr * ocx_zj(z, j);
+    }
+#pragma unroll
+    for (int j = 0; j < C; ++j) te[j] += (-yv) * ocx_zj(z, j);
+}

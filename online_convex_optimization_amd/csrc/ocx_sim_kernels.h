@@ -244,6 +244,19 @@ hipError_t ocx_launch_ftrl_exact_curve(const ocx_layout* L, const double* zt, co
                                        double* cum_e, double* comp_e, double* comp_f,
                                        double* cmp_out, int* regime, int* closed_out, int onepass,
                                        int norm, void* ws, hipStream_t st);
+// Its step-size form (ocx_ftrl_exact_grid.hip): FTRL for the M step sizes etas (HOST, read at
+// call time) beside one exact-FTL column, observed at the K checkpoints, in passes of `group`
+// (1, 2, 4; ocx_ftrl_exact_grid_instance) step sizes.  cum_r / comp_f [B][M][K]; the others as in
+// the curve form, written by the first pass.  ws: ocx_ftrl_exact_grid_ws_bytes(L, K, ne,
+// with_comp_f) bytes for passes of up to ne columns.
+bool ocx_ftrl_exact_grid_instance(const ocx_layout* L, int group);
+int ocx_ftrl_exact_grid_best_group(const ocx_layout* L);
+int64_t ocx_ftrl_exact_grid_ws_bytes(const ocx_layout* L, int64_t K, int64_t ne, int with_comp_f);
+hipError_t ocx_launch_ftrl_exact_grid(const ocx_layout* L, const double* zt, const double* yt,
+                                      const double* etas, int64_t M, const int64_t* ck, int64_t K,
+                                      double* cum_r, double* cum_e, double* comp_e, double* comp_f,
+                                      double* cmp_out, int* regime, int* closed_out, int onepass,
+                                      int norm, int group, void* ws, hipStream_t st);
 // float32 twin (algorithms.py, ocx_twin32.hip): P = 1 layouts, d <= 32
 // algo 0 FTRL, 1 FTL, 2 SMART (thresh[B]); clip: rows are raw g(T) normals to round to
 // float and clip in float32 (algorithms.py:157-160)

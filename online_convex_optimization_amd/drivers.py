@@ -349,6 +349,40 @@ def exact_case_regret_curves(title: str, T_grid: Sequence[int], *, runs: int, re
     return {"FTRL": out["ftrl"][:B].cpu().numpy(), "FTL (exact)": out["exact"][:B].cpu().numpy()}
 
 
+def exact_case_regret_grid(title: str, T_grid: Sequence[int], etas, *, runs: int,
+                           replicates: int, base_seed: int = 0, d: int = 5, p: float = 0.10,
+                           block_len: int = 20, lanes_per_seq: int = 1, device: int = 0,
+                           norm: str = "l2") -> Dict[str, np.ndarray]:
+    """exact_case_regret_curves for every FTRL step size of ``etas`` (a one-dimensional list of
+    reals), from ONE batch generated at horizon max(T_grid) and one grid call
+    (DeviceBatch.ftrl_vs_exact_curve_etas_general): {"FTRL": [runs * replicates, M, K],
+    "FTL (exact)": [runs * replicates, K]}.  "FTRL"[:, m, :] is exact_case_regret_curves' FTRL
+    line with eta0 = etas[m] in place of sqrt 2; the exact-FTL line does not depend on the step
+    size.
+
+    What the columns are depends on the family, as for exact_case_regret_curves.  For the
+    deterministic families (label flips, switching leaders) the prefix of the long sequence IS
+    the reference's sequence at each T, so column k holds the reference's numbers at T_k.  For
+    the random families (i.i.d., Massart) the reference draws a fresh sequence per T
+    (sequence_generation.py:61-62: the generator is seeded with T), so the grid is the anytime
+    regret on the longest horizon's rows — a different sample of the same distribution, not
+    the reference's per-T numbers."""
+    family, stream0 = CASE_FAMILIES[title]
+    grid = np.asarray(T_grid)
+    ck = engine._checkpoints(grid, int(grid.max()) if grid.size else 0)  # ValueError if bad
+    et = engine._etas(etas)
+    B, K, M = runs * replicates, int(ck.size), int(et.size)
+    if B == 0 or K == 0 or M == 0:
+        return {"FTRL": np.zeros((B, M, K)), "FTL (exact)": np.zeros((B, K))}
+    db = engine.DeviceBatch(B, int(ck[-1]), d, lanes_per_seq=lanes_per_seq, device=device)
+    run_idx = np.repeat(np.arange(runs), replicates)
+    rep_idx = np.tile(np.arange(replicates), runs)
+    db.generate_family(family, base_seed + 2025 * (run_idx + 1), stream0 + rep_idx, p=p,
+                       block_len=block_len)
+    out = db.ftrl_vs_exact_curve_etas_general(ck, et, norm=norm)
+    return {"FTRL": out["ftrl"][:B].cpu().numpy(), "FTL (exact)": out["exact"][:B].cpu().numpy()}
+
+
 def exact_evaluate_stream_with_stats(title: str, T_grid: Sequence[int], *, runs: int,
                                      replicates: int, base_seed: int = 0, device: int = 0,
                                      norm: str = "l2") -> Stats:

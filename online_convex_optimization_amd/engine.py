@@ -599,6 +599,58 @@ def ftrl_vs_exact_curve_batch(z, y, checkpoints, eta0: float = SQRT2, *, norm: s
     return out
 
 
+def ftrl_vs_exact_curve_etas_batch(z, y, checkpoints, etas, *, norm: str = "l2",
+                                   lanes_per_seq: int = LANES_BEST, device: int = 0,
+                                   check_regime: bool = True, with_ftl_comparator: bool = False):
+    """FTRL-vs-exact-FTL regret grid for B sequences (ocx_ftrl_vs_exact_curve_etas_batch):
+    ftrl_vs_exact_curve_batch for every eta0 of ``etas`` (a one-dimensional list of reals, any
+    order, duplicates allowed), each pass over z serving a group of FTRL columns beside one
+    exact-FTL column.
+
+    Returns a dict: ``ftrl``, ``cum_ftrl`` (and ``comp_ftl``) [B, M, K]; ``exact``,
+    ``cum_exact``, ``comp``, ``in_regime`` (bool), ``closed`` (int32) [B, K], ``action``
+    [B, K, d] and ``exact_gap_max``, which do not depend on the step size.  [:, m, :] and the
+    [B, K] arrays are ftrl_vs_exact_curve_batch(z, y, checkpoints, etas[m]) with the same
+    arguments.  With ``check_regime`` the pairs outside the closed form's regime are filled by
+    ONE general solve, whatever M is."""
+    code = _norm_code(norm)
+    z = _f64(z)
+    y = _f64(y)
+    B, T, d = _check_zy(z, y)
+    ck = _checkpoints(checkpoints, T)
+    et = _etas(etas)
+    K, M = int(ck.size), int(et.size)
+    cr, cmp_f = np.zeros((B, M, K)), np.zeros((B, M, K))
+    ce, cmp_e = np.zeros((B, K)), np.zeros((B, K))
+    act = np.zeros((B, K, d))
+    rg = np.zeros((B, K), dtype=np.int32)
+    closed = np.zeros((B, K), dtype=np.int32)
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    _lib.call("ocx_ftrl_vs_exact_curve_etas_batch", ptr(z), ptr(y), B, T, d, ptr(et), M,
+              ck.ctypes.data_as(_lib.c_i64p), K, ptr(cr), ptr(ce), ptr(cmp_e),
+              ptr(cmp_f) if with_ftl_comparator else None, ptr(act), rg.ctypes.data_as(i32p),
+              closed.ctypes.data_as(i32p), code, int(lanes_per_seq), int(device))
+    ok = rg.astype(bool)
+    worst = 0.0
+    bad = np.flatnonzero((~ok).any(axis=1)) if K and M else np.zeros(0, dtype=np.int64)
+    if check_regime and bad.size:
+        Tm = int(ck[-1])
+        res = exact_ball_solve(z[bad, :Tm], y[bad, :Tm], norm=norm, all_prefixes=True,
+                               device=device)
+        worst = check_certificates(res["obj"], res["gap"], res["info"])
+        gcum, gcomp = _general_curve_columns(res["step_loss"], res["obj"], ck)
+        m = ~ok[bad]                                   # only these pairs change
+        ce[bad] = np.where(m, gcum, ce[bad])
+        cmp_e[bad] = np.where(m, gcomp, cmp_e[bad])
+        act[bad] = np.where(m[:, :, None], res["actions"][:, ck], act[bad])
+    out = {"ftrl": cr - cmp_e[:, None, :], "exact": ce - cmp_e, "cum_ftrl": cr, "cum_exact": ce,
+           "comp": cmp_e, "action": act, "in_regime": ok, "closed": closed,
+           "exact_gap_max": worst}
+    if with_ftl_comparator:
+        out["comp_ftl"] = cmp_f
+    return out
+
+
 def gT_regrets(T: int, runs: int, *, base_seed: int = 0, d: int = 5, eta0: float = SQRT2,
                run0: int = 0, lanes_per_seq: int = LANES_BEST, device: int = 0) -> np.ndarray:
     """Regrets of FTRL on _rng(base_seed, T, run) sequences, run in [run0, run0+runs),
@@ -1538,10 +1590,24 @@ class DeviceBatch:
         self.exact_gap_max = 0.0
         if K == 0 or self.L.B == 0:
             return out
+        self._general_curve_fill(out, ck, norm, with_actions)
+        with self._on_stream():
+            out["ftrl"] = out["cum_ftrl"] - out["comp"]
+            out["exact"] = out["cum_exact"] - out["comp"]
+        return out
+
+    def _general_curve_fill(self, out, ck, norm: str, with_actions: bool):
+        """The general solver's numbers for the pairs of an exact curve or grid with
+        ``in_regime`` 0 (ftrl_vs_exact_curve_general): cum_exact, comp and action of ``out``
+        in place, the worst certified gap in self.exact_gap_max.  One solve over all prefixes
+        up to ck[-1] of the sequences with any such pair; none when every pair is in the
+        regime."""
+        torch = self.torch
+        d = int(self.L.d)
         with self._on_stream():
             out_of = out["in_regime"] == 0                  # [B, K]
             if not bool(out_of.any().item()):
-                return out
+                return
             bad = torch.nonzero(out_of.any(dim=1)).flatten()
             nb, Tm = int(bad.numel()), int(ck[-1])
             zb, yb = self.rows_of(bad)
@@ -1568,9 +1634,101 @@ class DeviceBatch:
             if with_actions:
                 acts = res["actions"][:, ckd, :]            # [nb, K, d]
                 out["action"][bad] = torch.where(m[:, :, None], acts, out["action"][bad])
-            out["ftrl"] = out["cum_ftrl"] - out["comp"]
+
+    def ftrl_vs_exact_curve_etas(self, checkpoints, etas, *, norm: str = "l2",
+                                 closed_comparator: Optional[bool] = None,
+                                 with_ftl_comparator: bool = False, with_actions: bool = False,
+                                 _group=None):
+        """FTRL-vs-exact-FTL regret grid of the resident batch (ocx_dev_ftrl_vs_exact_curve_etas,
+        async): ftrl_vs_exact_curve for every eta0 of ``etas`` (validated as in
+        simulate_alg_etas), each pass over z serving ocx_ftrl_exact_grid_group(L) FTRL columns
+        beside ONE exact-FTL column.  Returns a dict of device tensors: ``ftrl`` and
+        ``cum_ftrl`` [B, M, K] (with ``with_ftl_comparator`` also ``comp_ftl``), and ``exact``,
+        ``cum_exact``, ``comp``, ``in_regime``, ``closed`` [B, K] (with ``with_actions`` also
+        ``action`` [B, K, d]), which do not depend on the step size.  [:, m, :] and the [B, K]
+        tensors are ftrl_vs_exact_curve(checkpoints, etas[m], ...) bit for bit in the same
+        layout; the other arguments default as there.  (``_group`` forces the columns per pass:
+        1, 2 or 4 where the layout has that instance; the results do not depend on it.)"""
+        torch = self.torch
+        code = _norm_code(norm)
+        ck = _checkpoints(checkpoints, self.L.T)
+        et = _etas(etas)
+        K, M, B, d = int(ck.size), int(et.size), int(self.L.B), int(self.L.d)
+        if closed_comparator is None:
+            closed_comparator = not self.exact
+        flags = _lib.OCX_ALG_CLOSED_COMPARATOR if closed_comparator else 0
+        if self.best and self.L.chain:
+            flags |= _lib.OCX_ALG_TREE_SUMS  # as ftrl_vs_exact
+        nbytes = int(_lib.load().ocx_ftrl_exact_grid_workspace_bytes(
+            self._lp(), M, K, int(bool(with_ftl_comparator))))
+        if nbytes < 0:
+            _lib.check(nbytes, "ocx_ftrl_exact_grid_workspace_bytes")
+        with torch.cuda.device(self.device), self._on_stream():
+            ckd = torch.as_tensor(ck).to(self.device)
+            out = {"cum_ftrl": torch.zeros((B, M, K), dtype=torch.float64, device=self.device)}
+            for k in ("cum_exact", "comp"):
+                out[k] = torch.zeros((B, K), dtype=torch.float64, device=self.device)
+            if with_ftl_comparator:
+                out["comp_ftl"] = torch.zeros((B, M, K), dtype=torch.float64, device=self.device)
+            if with_actions:
+                out["action"] = torch.zeros((B, K, d), dtype=torch.float64, device=self.device)
+            for k in ("in_regime", "closed"):
+                out[k] = torch.zeros((B, K), dtype=torch.int32, device=self.device)
+            ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self.device)
+        if K and B and M:
+            self._call("ocx_dev_ftrl_vs_exact_curve_etas", self._lp(), self.z.data_ptr(),
+                       self.y.data_ptr(), ptr(et), M, ckd.data_ptr(), K,
+                       out["cum_ftrl"].data_ptr(), out["cum_exact"].data_ptr(),
+                       out["comp"].data_ptr(),
+                       out["comp_ftl"].data_ptr() if with_ftl_comparator else None,
+                       out["action"].data_ptr() if with_actions else None,
+                       out["in_regime"].data_ptr(), out["closed"].data_ptr(), code, flags,
+                       0 if _group is None else int(_group), ws.data_ptr(), ws.numel() * 8,
+                       self._sp)
+        with self._on_stream():
+            out["ftrl"] = out["cum_ftrl"] - out["comp"][:, None, :]
+            out["exact"] = out["cum_exact"] - out["comp"]
+        self._keep_exact_grid = self._hold(ckd, ws)
+        return out
+
+    def ftrl_vs_exact_curve_etas_general(self, checkpoints, etas, *, norm: str = "l2",
+                                         closed_comparator: Optional[bool] = None,
+                                         with_ftl_comparator: bool = False,
+                                         with_actions: bool = False, _group=None):
+        """ftrl_vs_exact_curve_etas with every pair's exact side valid, as
+        ftrl_vs_exact_curve_general: the pairs with ``in_regime`` 0 get the general solver's
+        cum_exact / comp / action — ONE solve over all prefixes up to the largest checkpoint for
+        the sequences with any such pair, whatever M is — and ``ftrl`` (every step size) and
+        ``exact`` are taken again.  [:, m, :] is ftrl_vs_exact_curve_general(checkpoints,
+        etas[m], ...).  Certificates are checked (the worst gap is left in self.exact_gap_max).
+        Synchronises once."""
+        out = self.ftrl_vs_exact_curve_etas(checkpoints, etas, norm=norm,
+                                            closed_comparator=closed_comparator,
+                                            with_ftl_comparator=with_ftl_comparator,
+                                            with_actions=with_actions, _group=_group)
+        self.exact_gap_max = 0.0
+        if out["cum_ftrl"].numel() == 0:
+            return out
+        self._general_curve_fill(out, _checkpoints(checkpoints, self.L.T), norm, with_actions)
+        with self._on_stream():
+            out["ftrl"] = out["cum_ftrl"] - out["comp"][:, None, :]
             out["exact"] = out["cum_exact"] - out["comp"]
         return out
+
+    def ftrl_vs_exact_etas(self, etas, *, norm: str = "l2",
+                           closed_comparator: Optional[bool] = None,
+                           with_ftl_comparator: bool = False, with_actions: bool = False,
+                           _group=None):
+        """Step-size sweep of ftrl_vs_exact on the resident batch: the grid at checkpoints = [T]
+        with the horizon axis dropped (the same kernel).  ``ftrl``, ``cum_ftrl`` (``comp_ftl``)
+        [B, M]; ``exact``, ``cum_exact``, ``comp``, ``in_regime``, ``closed`` [B] (``action``
+        [B, d]); column m is ftrl_vs_exact(etas[m]) bit for bit."""
+        out = self.ftrl_vs_exact_curve_etas([self.L.T], etas, norm=norm,
+                                            closed_comparator=closed_comparator,
+                                            with_ftl_comparator=with_ftl_comparator,
+                                            with_actions=with_actions, _group=_group)
+        three = ("ftrl", "cum_ftrl", "comp_ftl")
+        return {k: (v[:, :, 0] if k in three else v[:, 0]) for k, v in out.items()}
 
     def exact_comparison_curves(self, checkpoints, eta0: float = SQRT2, norm: str = "l2"):
         """The two lines of the reference's exact comparison figure (exact_ftl_driver.py:
