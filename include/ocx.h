@@ -71,7 +71,9 @@
  * ocx_dev_max_regret_cols), and for the SMART regret-grid symbols (ocx_smart_grid_group,
  * ocx_dev_simulate_smart_grid, ocx_simulate_smart_grid_batch), and for the FTRL-vs-exact-FTL
  * regret-grid symbols (ocx_ftrl_exact_grid_group, ocx_ftrl_exact_grid_workspace_bytes,
- * ocx_dev_ftrl_vs_exact_curve_etas, ocx_ftrl_vs_exact_curve_etas_batch).
+ * ocx_dev_ftrl_vs_exact_curve_etas, ocx_ftrl_vs_exact_curve_etas_batch), and for the label-bit
+ * symbols (ocx_label_bits_words, ocx_dev_pack_bits, ocx_dev_gen_gT_bits,
+ * ocx_dev_simulate_alg_bits).
  *
  * Checking the ABI: one intermediate 0.1.x tree exported ocx_ftrl_vs_exact_batch WITH a
  * `norm` argument under the same symbol and the same version number as the release without
@@ -105,7 +107,15 @@ typedef enum ocx_status {
  * streams open than one region per wave:
  *   z_tiled[((k*G + g)*T + t)*128 + L*2 + e] = z[b][t][c*C + 2k + e]
  *   y_tiled[(g*T + t)*S + s]                 = y[b][t]
- * Padding (coordinates j >= d, sequences b >= B) holds zeros. */
+ * Padding (coordinates j >= d, sequences b >= B) holds zeros.
+ *
+ * The label-bit tile (optional, beside y_tiled; ocx_label_bits_words(L) 64-bit words, 1/64 of
+ * y_tiled): one word per wave-group g, 64-step block k < ceil(T/64) and sequence slot s < S,
+ *   y_bits[(g*ceil(T/64) + k)*S + s]  bit (t mod 64)  =  (y[b = g*S + s][64k + (t mod 64)] == +1)
+ * with the bits at t >= T and of padding sequences 0.  It stands for y_tiled only where every
+ * label of a real sequence is exactly +1 or -1 (the g(T) sampler's are); the pipelined
+ * FTRL / FTL step then reads one bit per label instead of one double (ocx_dev_simulate_alg_bits).
+ * The layout holds for every P and S. */
 typedef struct ocx_layout {
     int64_t B, T, d;  /* logical sizes */
     int32_t P;        /* lanes per sequence (1..64, power of two) */
@@ -130,6 +140,8 @@ int ocx_device_count(int* count);
 int ocx_release_buffers(int device);
 /* Fill *out for (B, T, d) and a lanes_per_seq request (see Conventions). */
 int ocx_layout_init(int64_t B, int64_t T, int64_t d, int lanes_per_seq, ocx_layout* out);
+/* 64-bit words in the layout's label-bit tile: G * ceil(T/64) * S (negative: an error). */
+int64_t ocx_label_bits_words(const ocx_layout* L);
 
 /* ---- host entry points (numpy buffers in, results out) ------------------- */
 
@@ -350,10 +362,20 @@ int ocx_twin32_gT_regrets(uint64_t base_seed, int64_t T, int64_t run0, int64_t R
 int ocx_dev_pack(const ocx_layout* L, const double* z, const double* y, double* z_tiled,
                  double* y_tiled, void* stream);
 
+/* ocx_dev_pack that also writes the label-bit tile y_bits (device, ocx_label_bits_words(L)
+ * words) and *not_unit (device int32): 1 if any label of a real sequence is not exactly +1 or
+ * -1 — y_bits must then not be used — else 0. */
+int ocx_dev_pack_bits(const ocx_layout* L, const double* z, const double* y, double* z_tiled,
+                      double* y_tiled, uint64_t* y_bits, int32_t* not_unit, void* stream);
+
 /* fast_algorithms.py:231-239 sampler on device: sequence b of the layout is
  * _rng(base_seed, T, run0 + b) → clipped N(0, I_d) rows and ±1 labels. */
 int ocx_dev_gen_gT(const ocx_layout* L, uint64_t base_seed, int64_t run0, double* z_tiled,
                    double* y_tiled, void* stream);
+/* ocx_dev_gen_gT that also fills the label-bit tile y_bits (nullable: ocx_dev_gen_gT); z_tiled
+ * and y_tiled are written exactly as by ocx_dev_gen_gT. */
+int ocx_dev_gen_gT_bits(const ocx_layout* L, uint64_t base_seed, int64_t run0, double* z_tiled,
+                        double* y_tiled, uint64_t* y_bits, void* stream);
 
 /* sequence_generation.py families on device, sequence b of the layout:
  *   family 1  make_random_iid_stream (:54-69): _rng(run_seeds[b], T, stream_ids[b]),
@@ -394,6 +416,19 @@ int ocx_dev_simulate_alg_ex(const ocx_layout* L, const double* z_tiled, const do
                             int alg_flag, double eta0, const double* comparator, double* regret,
                             double* cum_loss, double* comp_loss, double* x_last, int flags,
                             int32_t* closed_out, void* stream);
+/* ocx_dev_simulate_alg_ex with the label-bit tile: y_bits (device, nullable) must hold the bits
+ * of y_tiled's labels, all of a real sequence's exactly +-1 (ocx_dev_gen_gT_bits, or
+ * ocx_dev_pack_bits with *not_unit == 0).  Where the launch is the instance of the pipelined step
+ * built for it (the persistent 8 x 8 instance: a d = 64 batch of more wave-groups than are
+ * resident at once) the kernel reads the bits instead of y_tiled's doubles, 512.125 instead of
+ * 520 bytes per time step (measured: 512.17); every
+ * other launch, and y_bits == NULL, is ocx_dev_simulate_alg_ex.  y_tiled is required either way.
+ * Same results bit for bit.  OCX_LABEL_BITS=0 in the environment keeps every launch on y_tiled. */
+int ocx_dev_simulate_alg_bits(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                              const uint64_t* y_bits, int alg_flag, double eta0,
+                              const double* comparator, double* regret, double* cum_loss,
+                              double* comp_loss, double* x_last, int flags, int32_t* closed_out,
+                              void* stream);
 
 /* Regret curves: fast_algorithms.py:88-115 observed at K checkpoint horizons in one pass.
  * FTRL and FTL are online, so the first t steps of a run on (z, y) are the run on
@@ -893,7 +928,6 @@ int ocx_dev_max_regret(const double* regrets, int64_t B, double* gmax, void* str
 int ocx_dev_gen_simulate(const ocx_layout* L, uint64_t base_seed, int64_t run0, int64_t nbatch,
                          double* z_tiled, double* y_tiled, double eta0, double* regret,
                          double* gmax, uint32_t flags, int64_t sub_seqs, void* stream);
-
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,12 @@ int ocx_test_alg_range(const ocx_layout* L, const double* z_tiled, const double*
 int ocx_test_alg_pipe_persistent(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
                                  int ftl, double eta0, int onepass, int64_t nwaves, double* regret,
                                  double* cum, double* comp, int32_t* closed_out, void* stream);
+/* The same with the label-bit tile y_bits (nullable): the persistent instance that reads it. */
+int ocx_test_alg_pipe_persistent_bits(const ocx_layout* L, const double* z_tiled,
+                                      const double* y_tiled, const uint64_t* y_bits, int ftl,
+                                      double eta0, int onepass, int64_t nwaves, double* regret,
+                                      double* cum, double* comp, int32_t* closed_out,
+                                      void* stream);
 
 /* ocx_dev_simulate_alg_etas with the group size forced to `group` (1, 2 or 4) instead of
  * ocx_etas_group's choice, so a test reaches every instantiated form whatever the dispatcher

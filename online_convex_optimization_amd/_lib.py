@@ -75,6 +75,14 @@ SIGNATURES = {
     "ocx_gT_max": (c_int, [c_u64, c_i64, c_i64, c_i64, c_i64, c_double, c_int, c_int, c_dp]),
     "ocx_dev_pack": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "ocx_dev_gen_gT": (c_int, [ctypes.POINTER(Layout), c_u64, c_i64, c_vp, c_vp, c_vp]),
+    "ocx_label_bits_words": (c_i64, [ctypes.POINTER(Layout)]),
+    "ocx_dev_pack_bits": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp]),
+    "ocx_dev_gen_gT_bits": (c_int, [ctypes.POINTER(Layout), c_u64, c_i64, c_vp, c_vp, c_vp,
+                                    c_vp]),
+    "ocx_dev_simulate_alg_bits": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_vp, c_int,
+                                          c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp,
+                                          c_vp]),
     "ocx_dev_gen_family": (c_int, [ctypes.POINTER(Layout), c_int, c_vp, c_vp, c_double, c_i64,
                                    c_vp, c_vp, c_vp]),
     "ocx_dev_simulate_alg": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_int, c_double, c_vp,
@@ -181,6 +189,9 @@ TEST_SIGNATURES = {
                                    c_i64, c_vp, c_vp, c_vp]),
     "ocx_test_alg_pipe_persistent": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_int, c_double,
                                              c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "ocx_test_alg_pipe_persistent_bits": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_vp, c_int,
+                                                  c_double, c_int, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                                  c_vp]),
     "ocx_test_simulate_alg_etas": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_dp, c_i64, c_vp,
                                            c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
     "ocx_test_simulate_alg_curve_etas": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_dp, c_i64,

@@ -56,6 +56,9 @@ struct PipeArgs {
     double* state;   // chunked runs: the carried state (nullable: whole run)
     int* bad;        // chunked runs: set when a sequence needs the second pass
     unsigned long long* gmax;  // nullable: g(T) = max(0, max regret) folded in (bit pattern)
+    // nullable: the label-bit tile (BITS instances read it instead of yt).  Last, so that every
+    // other field keeps its kernel-argument offset and the float64 instances their code.
+    const uint64_t* yb;
 };
 
 #ifndef OCX_PIPE_WAVE_CLOCK  // diagnostic build: per-wave clocks instead of cum / comp (below)
@@ -76,7 +79,18 @@ struct PipeNoObserver {};
 // One wave-group's run: group wv (wave-uniform) of the launch's gn.  Every piece of state is
 // local to the call, so a wave that runs several groups (alg_pipe_body, LOOP) starts each from
 // scratch: the ring is filled again (one load latency per group) and nothing is carried over.
-template <int C, int P, int NB, bool FTL, bool RT, bool CHUNK, class Obs>
+// BITS: the labels come from the label-bit tile (include/ocx.h: one 64-bit word per sequence
+// and 64-step block, bit t mod 64 set where y_t = +1) instead of y_tiled's doubles: no label
+// load and no label ring slot per step; the lane loads its sequence's word one block ahead
+// (clamped at the horizon's last block, as the look-ahead is) and forms y_t = ±1.0 from bit
+// t mod 64 with a wave-uniform shift.  The same doubles reach the same arithmetic, so the
+// results are the float64 path's bit for bit wherever every label of a real sequence is ±1.
+// A padding sequence (b >= B) differs inside the wave: its bits are 0, so it runs with y = −1.0
+// where y_tiled gives it 0.0, and with its all-zero rows it stays `clean`.  Nothing of it gets
+// out: every vote and output is gated on `live` (closed = onepass && (clean || !live), so it
+// never asks for the second pass on either path; gmax, regret, cum, comp, closed_out are
+// written for live sequences only), and θ stays 0 either way (g·z = 0).
+template <int C, int P, int NB, bool FTL, bool RT, bool CHUNK, class Obs, bool BITS = false>
 __device__ __forceinline__ void alg_pipe_group(const PipeArgs& a, const int64_t wv, Obs& obs) {
     static_assert(P >= 2 && NB >= 4, "butterfly layouts, a ring holding z_{t-1} .. z_{t+1}");
     constexpr bool OBS = !std::is_same<typename std::decay<Obs>::type, PipeNoObserver>::value;
@@ -105,6 +119,12 @@ __device__ __forceinline__ void alg_pipe_group(const PipeArgs& a, const int64_t 
     const ocx_d2* __restrict__ zg = reinterpret_cast<const ocx_d2*>(a.zt) + (g * T + t0) * tstride;
     const int64_t kst = a.G * T * 64;  // plane stride (pairs k)
     const double* __restrict__ yg = a.yt + (g * T + t0) * S;
+    // BITS: this lane's word of block kb at ybg[kb * S]; KB blocks in the horizon
+    const int64_t KB = (T + 63) >> 6;
+    const uint64_t* __restrict__ ybg = BITS ? a.yb + g * KB * S + s : nullptr;
+    auto ybit = [](uint64_t w, int sh) -> double {  // bit sh of w: 1 -> +1.0, 0 -> -1.0
+        return __hiloint2double((int)(0xBFF00000u ^ ((uint32_t)(w >> sh) << 31)), 0);
+    };
     // word i of this lane's carried state (formed where used: nothing stays live over the loop)
     auto stw = [&](int i) -> double& { return a.state[(g * NS + i) * 64 + lane]; };
 
@@ -117,7 +137,11 @@ __device__ __forceinline__ void alg_pipe_group(const PipeArgs& a, const int64_t 
     // (ocx_ring_loop<NB, true>) refill that slot only after step t.  At t = 0 that slot is
     // zero (g_{-1} = 0 multiplies it); a later chunk restores z_{t0-1} there.
     ocx_d2 zb[NB][K];
-    double yb[NB];
+    double yb[BITS ? 1 : NB];
+    uint64_t ywc = 0, ywn = 0;  // BITS: the current block's word, the next block's
+    if constexpr (BITS) {
+        if (tn > 0) ywn = ybg[(t0 >> 6) * S];
+    }
     if (first) {
 #pragma unroll
         for (int j = 0; j < C; ++j) th[j] = 0.0;
@@ -146,14 +170,21 @@ __device__ __forceinline__ void alg_pipe_group(const PipeArgs& a, const int64_t 
             zb[slot][k] = row[k * kst + lane];
 #endif
         }
-        yb[slot] = yg[tl * S + s];
+        if constexpr (!BITS) yb[slot] = yg[tl * S + s];
     };
 
     double scv = 0.0;  // −η0/√(t+1+lane) for the 64 steps from the last multiple of 64
 
     ocx_ring_loop<NB, true, IT>(tn, load, [&](int u, int64_t tl) {
         const int64_t t = t0 + tl;
-        if ((tl & 63) == 0) ocx_pipe_refresh<FTL>(t, lane, eta0, scv, th, U);
+        if ((tl & 63) == 0) {
+            ocx_pipe_refresh<FTL>(t, lane, eta0, scv, th, U);
+            if constexpr (BITS) {
+                const int64_t kn = (t >> 6) + 1;
+                ywc = ywn;
+                ywn = ybg[(kn < KB ? kn : KB - 1) * S];
+            }
+        }
         // ---- chain: g_{t-1} → z_t·θ_t, ||θ_t||² → q_t → g_t
         const double zth = __builtin_fma(gp, Bz, A);
         double tth = __builtin_fma(gp, __builtin_fma(gp, W, 2.0 * V), U);
@@ -168,9 +199,9 @@ __device__ __forceinline__ void alg_pipe_group(const PipeArgs& a, const int64_t 
             qt = ocx_pipe_q_ftrl<RT>(ocx_readlane(scv, (int)(tl & 63)), q_raw, n_raw);
         else
             qt = ocx_pipe_q_ftl<C, P>(th, q_raw, n_raw, tth, live);
-        const double yv = yb[u];
+        const double yv = BITS ? ybit(ywc, (int)(tl & 63)) : yb[u];
         const double gq = ocx_loss_grad(qt, yv, cum);
-        ocx_cert_grad(clean, yv, gq);
+        ocx_cert_grad<BITS>(clean, yv, gq);
         // ---- off the chain; z_{t+1} is in flight since NB-2 steps
         ocx_pipe_advance<P>(th, zb[u], zb[(u + 1) % NB], a.onepass, zth, tth, gq, A, Bz, U, V, W, gp,
                             clean);
@@ -214,12 +245,22 @@ __device__ __forceinline__ void alg_pipe_group(const PipeArgs& a, const int64_t 
         if (first) {  // zg, yg: row 0
             double xs[C];
             ocx_action_ftl<C, P, false>(th, xs, lane);
-            ocx_ring_loop<NB, false, IT>(T, load, [&](int u, int64_t) {
+            if constexpr (BITS) {
+                if (T > 0) ywn = ybg[0];  // (T = 0: the tile has no word)
+            }
+            ocx_ring_loop<NB, false, IT>(T, load, [&](int u, int64_t tl) {
+                if constexpr (BITS) {
+                    if ((tl & 63) == 0) {
+                        const int64_t kn = (tl >> 6) + 1;
+                        ywc = ywn;
+                        ywn = ybg[(kn < KB ? kn : KB - 1) * S];
+                    }
+                }
                 double p[C];
 #pragma unroll
                 for (int j = 0; j < C; ++j) p[j] = ocx_zj(zb[u], j) * xs[j];
                 const double qq = ocx_total<C, P, false>(p, lane);
-                comp += 0.5 * fabs(qq - yb[u]);
+                comp += 0.5 * fabs(qq - (BITS ? ybit(ywc, (int)(tl & 63)) : yb[u]));
             });
         } else if constexpr (CHUNK) {
             comp = __builtin_nan("");
@@ -269,20 +310,20 @@ __device__ __forceinline__ void alg_pipe_group(const PipeArgs& a, const int64_t 
 // runs groups w, w + gstride, ... < gn, one after the other — a plain loop, no hand-off between
 // waves; a wave beyond gstride (the last block's spare slots) leaves.
 template <int C, int P, int NB, bool FTL, bool RT, bool CHUNK = false, class Obs = PipeNoObserver,
-          bool LOOP = false>
+          bool LOOP = false, bool BITS = false>
 __device__ __forceinline__ void alg_pipe_body(const PipeArgs& a, Obs&& obs = Obs{}) {
     // wave-uniform, provably (readfirstlane): the tile bases live in SGPRs and every load
     // is an SGPR base + the lane's constant offset, with no per-load address arithmetic
     if constexpr (!LOOP) {
         const int64_t wv = (int64_t)__builtin_amdgcn_readfirstlane((int)ocx_pipe_wave_id(a.gn));
         if (wv >= a.gn) return;
-        alg_pipe_group<C, P, NB, FTL, RT, CHUNK>(a, wv, obs);
+        alg_pipe_group<C, P, NB, FTL, RT, CHUNK, Obs, BITS>(a, wv, obs);
     } else {
         static_assert(!CHUNK, "a chunked run carries one group's state per wave");
         const int64_t w0 = (int64_t)__builtin_amdgcn_readfirstlane((int)ocx_wave_id());
         if (w0 >= a.gstride) return;
         for (int64_t wv = w0; wv < a.gn; wv += a.gstride)
-            alg_pipe_group<C, P, NB, FTL, RT, CHUNK>(a, wv, obs);
+            alg_pipe_group<C, P, NB, FTL, RT, CHUNK, Obs, BITS>(a, wv, obs);
     }
 }
 

@@ -44,9 +44,26 @@
 #include "ocx_internal.h"
 #include "ocx_sim_kernels.h"
 
-template <int C, int P, int NB, bool FTL, int MINW = 1, bool CHUNK = false, bool LOOP = false>
+// BITS: the instances that read the label-bit tile (ocx_alg_pipe.h) — the persistent 8 x 8
+// instance, FTRL and FTL: what a resident d = 64 batch of more groups than one round holds
+// launches (the bench).  Every other launch keeps y_tiled: the full 8 x 8 form measured slower
+// from bits on the few-wave batches (4 900 x 1e5 x 64: 39.8 -> 45.5 ms; a latency-bound wave
+// pays for the block-boundary word load), and the lean and chunked forms run beside a
+// generator that would pay more for writing the tile than the pass saves (DESIGN.md §3.1,
+// §3.2).  Resource reports: profiles/label_bits_resources.txt.
+template <int C, int P, int NB, bool FTL, int MINW = 1, bool CHUNK = false, bool LOOP = false,
+          bool BITS = false>
 __global__ __launch_bounds__(OCX_BLOCK, MINW) void ocx_alg_pipe_kernel(PipeArgs a) {
-    alg_pipe_body<C, P, NB, FTL, pipe_rt<C, P, MINW>(), CHUNK, PipeNoObserver, LOOP>(a);
+    alg_pipe_body<C, P, NB, FTL, pipe_rt<C, P, MINW>(), CHUNK, PipeNoObserver, LOOP, BITS>(a);
+}
+
+// OCX_LABEL_BITS=0: every launch reads y_tiled's doubles (A/B inside one build)
+static bool label_bits_enabled() {
+    static const bool on = [] {
+        const char* e = std::getenv("OCX_LABEL_BITS");
+        return !e || std::atoi(e) != 0;
+    }();
+    return on;
 }
 
 // ---------------------------------------------------------------------------
@@ -120,7 +137,7 @@ hipError_t pers_shape(K kern, int dev, int cus, int wps, int bw, PersGeom& gm) {
 }
 
 template <int C, int P>
-PersGeom pers_geometry(int ftl) {
+PersGeom pers_geometry(int ftl, bool bits) {
     constexpr int NB = pipe_nb<C>(P), NBP = OCX_PIPE_PERS_NB, MW = OCX_PIPE_PERS_MINW;
     PersGeom gm;
     int dev = 0, cus = 0;
@@ -134,7 +151,7 @@ PersGeom pers_geometry(int ftl) {
     static std::mutex mu;
     static std::map<std::pair<int, int>, PersGeom> cache;
     std::lock_guard<std::mutex> lk(mu);
-    const auto key = std::make_pair(dev, ftl);
+    const auto key = std::make_pair(dev, (ftl ? 1 : 0) | (bits ? 2 : 0));
     const auto it = cache.find(key);
     if (it != cache.end()) return it->second;
 #endif
@@ -145,8 +162,13 @@ PersGeom pers_geometry(int ftl) {
                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, ocx_alg_pipe_kernel<C, P, NB, false>, 256, 0);
     if (gm.err != hipSuccess) return gm;
     gm.round = (int64_t)q * 4 * cus;
-    gm.err = ftl ? pers_shape(ocx_alg_pipe_kernel<C, P, NBP, true, MW, false, true>, dev, cus, wps, bw, gm)
-                 : pers_shape(ocx_alg_pipe_kernel<C, P, NBP, false, MW, false, true>, dev, cus, wps, bw, gm);
+    // (round: the float64 form's in both cases, so the labels' form never moves the policy)
+    if (bits)
+        gm.err = ftl ? pers_shape(ocx_alg_pipe_kernel<C, P, NBP, true, MW, false, true, true>, dev, cus, wps, bw, gm)
+                     : pers_shape(ocx_alg_pipe_kernel<C, P, NBP, false, MW, false, true, true>, dev, cus, wps, bw, gm);
+    else
+        gm.err = ftl ? pers_shape(ocx_alg_pipe_kernel<C, P, NBP, true, MW, false, true>, dev, cus, wps, bw, gm)
+                     : pers_shape(ocx_alg_pipe_kernel<C, P, NBP, false, MW, false, true>, dev, cus, wps, bw, gm);
 #if !OCX_PIPE_PERS_TUNE
     if (gm.err == hipSuccess) cache.emplace(key, gm);
 #endif
@@ -164,7 +186,11 @@ hipError_t launch_pipe_persistent(PipeArgs a, int ftl, int64_t nwaves, const Per
 #endif
     a.gstride = nwaves > 0 ? nwaves : gm.nw;
     const dim3 grid = ocx_grid(a.gstride, bw), block(64 * bw);
-    if (ftl)
+    if (a.yb && ftl)
+        hipLaunchKernelGGL((ocx_alg_pipe_kernel<C, P, NBP, true, MW, false, true, true>), grid, block, gm.lds, st, a);
+    else if (a.yb)
+        hipLaunchKernelGGL((ocx_alg_pipe_kernel<C, P, NBP, false, MW, false, true, true>), grid, block, gm.lds, st, a);
+    else if (ftl)
         hipLaunchKernelGGL((ocx_alg_pipe_kernel<C, P, NBP, true, MW, false, true>), grid, block, gm.lds, st, a);
     else
         hipLaunchKernelGGL((ocx_alg_pipe_kernel<C, P, NBP, false, MW, false, true>), grid, block, gm.lds, st, a);
@@ -178,7 +204,7 @@ hipError_t launch_pipe_cp(const PipeArgs& a, int ftl, hipStream_t st) {
         // more groups than one round holds; every smaller batch (the few-wave T = 1e5 shapes,
         // the capacity-limited ones) keeps its one-group-per-wave launch below
         if (!a.state) {
-            const PersGeom gm = pers_geometry<C, P>(ftl);
+            const PersGeom gm = pers_geometry<C, P>(ftl, a.yb != nullptr);
             if (gm.err != hipSuccess) return gm.err;
             if (a.gn > gm.round) return launch_pipe_persistent<C, P>(a, ftl, 0, gm, st);
         }
@@ -201,11 +227,13 @@ hipError_t launch_pipe(const ocx_layout* L, const PipeArgs& a, int ftl, hipStrea
     });
 }
 
-PipeArgs pipe_args(const ocx_layout* L, const double* zt, const double* yt, double eta0,
-                   double* reg, double* cum, double* comp, int* closed_out, int onepass) {
+PipeArgs pipe_args(const ocx_layout* L, const double* zt, const double* yt, const uint64_t* yb,
+                   double eta0, double* reg, double* cum, double* comp, int* closed_out,
+                   int onepass) {
     PipeArgs a{};
     a.zt = zt;
     a.yt = yt;
+    a.yb = label_bits_enabled() ? yb : nullptr;
     a.B = L->B;
     a.T = L->T;
     a.G = L->G;
@@ -231,9 +259,9 @@ bool ocx_pipe_supported(const ocx_layout* L) {
 
 hipError_t ocx_launch_alg_pipe(const ocx_layout* L, const double* zt, const double* yt, int ftl,
                                double eta0, double* reg, double* cum, double* comp,
-                               int* closed_out, int onepass, hipStream_t st) {
+                               int* closed_out, int onepass, hipStream_t st, const uint64_t* yb) {
     if (L->G == 0) return hipSuccess;
-    return launch_pipe(L, pipe_args(L, zt, yt, eta0, reg, cum, comp, closed_out, onepass), ftl, st);
+    return launch_pipe(L, pipe_args(L, zt, yt, yb, eta0, reg, cum, comp, closed_out, onepass), ftl, st);
 }
 
 bool ocx_pipe_persistent_supported(const ocx_layout* L) {
@@ -245,13 +273,13 @@ bool ocx_pipe_persistent_supported(const ocx_layout* L) {
 hipError_t ocx_launch_alg_pipe_persistent(const ocx_layout* L, const double* zt, const double* yt,
                                           int ftl, double eta0, double* reg, double* cum,
                                           double* comp, int* closed_out, int onepass,
-                                          int64_t nwaves, hipStream_t st) {
+                                          int64_t nwaves, hipStream_t st, const uint64_t* yb) {
     if (!ocx_pipe_persistent_supported(L) || nwaves <= 0) return hipErrorInvalidValue;
     if (L->G == 0) return hipSuccess;
-    const PersGeom gm = pers_geometry<8, 8>(ftl);
+    const PipeArgs a = pipe_args(L, zt, yt, yb, eta0, reg, cum, comp, closed_out, onepass);
+    const PersGeom gm = pers_geometry<8, 8>(ftl, a.yb != nullptr);
     if (gm.err != hipSuccess) return gm.err;
-    return launch_pipe_persistent<8, 8>(pipe_args(L, zt, yt, eta0, reg, cum, comp, closed_out, onepass),
-                                        ftl, nwaves, gm, st);
+    return launch_pipe_persistent<8, 8>(a, ftl, nwaves, gm, st);
 }
 
 int64_t ocx_pipe_state_doubles(const ocx_layout* L) {
@@ -307,7 +335,7 @@ hipError_t ocx_launch_alg_pipe_lean(const ocx_layout* L, const double* zt, const
                                     int64_t gn, unsigned long long* gmax, hipStream_t st) {
     if (gn <= 0) return hipSuccess;
     if (g0 < 0 || g0 + gn > L->G) return hipErrorInvalidValue;
-    PipeArgs a = pipe_args(L, zt, yt, eta0, reg, nullptr, nullptr, nullptr, onepass);
+    PipeArgs a = pipe_args(L, zt, yt, nullptr, eta0, reg, nullptr, nullptr, nullptr, onepass);
     a.g0 = g0;
     a.gn = gn;
     a.gmax = gmax;
@@ -324,7 +352,7 @@ hipError_t ocx_launch_alg_pipe_chunk(const ocx_layout* L, const double* zt, cons
     // onepass only: a chunk after the first cannot stream the second comparator pass
     if (t0 < 0 || t0 % 64 != 0 || t0 + tn > L->T || !state || !onepass || !ocx_pipe_supported(L))
         return hipErrorInvalidValue;
-    PipeArgs a = pipe_args(L, zt, yt, eta0, reg, nullptr, nullptr, nullptr, onepass);
+    PipeArgs a = pipe_args(L, zt, yt, nullptr, eta0, reg, nullptr, nullptr, nullptr, onepass);
     a.t0 = t0;
     a.tn = tn;
     a.state = state;

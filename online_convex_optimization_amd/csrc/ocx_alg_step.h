@@ -47,8 +47,12 @@ __device__ __forceinline__ double ocx_loss_grad(const double& q, const double& y
 
 // The closed form's certificate, label and sub-gradient part: y_t = ±1 and g_t = −y_t/2 (then
 // θ_T = −½ Σ y_t z_t exactly).  The row part (||z_t|| <= 1): ocx_row_in_ball, ocx_pipe_advance.
+// UNIT: y was formed as ±1.0 from a label bit (ocx_alg_pipe.h, BITS), so |y| = 1 holds by
+// construction and only the sub-gradient is tested.
+template <bool UNIT = false>
 __device__ __forceinline__ void ocx_cert_grad(bool& clean, const double& y, const double& gq) {
-    clean = clean && fabs(y) == 1.0 && gq == -0.5 * y;
+    if constexpr (UNIT) clean = clean && gq == -0.5 * y;
+    else clean = clean && fabs(y) == 1.0 && gq == -0.5 * y;
 }
 
 // ---------------------------------------------------------------------------

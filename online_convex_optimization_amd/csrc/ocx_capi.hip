@@ -337,14 +337,36 @@ int ocx_dev_pack(const ocx_layout* L, const double* z, const double* y, double* 
     return OCX_OK;
 }
 
-int ocx_dev_gen_gT(const ocx_layout* L, uint64_t base_seed, int64_t run0, double* z_tiled,
-                   double* y_tiled, void* stream) {
+int64_t ocx_label_bits_words(const ocx_layout* L) {
+    if (int rc = check_layout(L)) return rc;
+    if (L->B < 0 || L->T < 0 || L->G != ceil_div(L->B, L->S))
+        return fail(OCX_E_INVALID, "corrupt layout");
+    return ocx_label_bits_words_of(L);
+}
+
+int ocx_dev_pack_bits(const ocx_layout* L, const double* z, const double* y, double* z_tiled,
+                      double* y_tiled, uint64_t* y_bits, int32_t* not_unit, void* stream) {
+    if (!not_unit) return fail(OCX_E_INVALID, "NULL not_unit");
+    if (L && ocx_label_bits_words(L) > 0 && !y_bits) return fail(OCX_E_INVALID, "NULL y_bits");
+    if (int rc = ocx_dev_pack(L, z, y, z_tiled, y_tiled, stream)) return rc;
+    StreamDevice sd_(stream);
+    OCX_HIP(ocx_launch_pack_ybits(L, y, y_bits, not_unit, (hipStream_t)stream));
+    return OCX_OK;
+}
+
+int ocx_dev_gen_gT_bits(const ocx_layout* L, uint64_t base_seed, int64_t run0, double* z_tiled,
+                        double* y_tiled, uint64_t* y_bits, void* stream) {
     StreamDevice sd_(stream);
     if (int rc = check_layout(L)) return rc;
     if (run0 < 0) return fail(OCX_E_INVALID, "run0 < 0");
     if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL buffer");
-    OCX_HIP(ocx_launch_gen_gT(L, base_seed, run0, z_tiled, y_tiled, (hipStream_t)stream));
+    OCX_HIP(ocx_launch_gen_gT(L, base_seed, run0, z_tiled, y_tiled, (hipStream_t)stream, y_bits));
     return OCX_OK;
+}
+
+int ocx_dev_gen_gT(const ocx_layout* L, uint64_t base_seed, int64_t run0, double* z_tiled,
+                   double* y_tiled, void* stream) {
+    return ocx_dev_gen_gT_bits(L, base_seed, run0, z_tiled, y_tiled, nullptr, stream);
 }
 
 int ocx_dev_gen_family(const ocx_layout* L, int family, const uint64_t* run_seeds,
@@ -379,6 +401,15 @@ int ocx_dev_simulate_alg_ex(const ocx_layout* L, const double* z_tiled, const do
                             int alg_flag, double eta0, const double* comparator, double* regret,
                             double* cum_loss, double* comp_loss, double* x_last, int flags,
                             int32_t* closed_out, void* stream) {
+    return ocx_dev_simulate_alg_bits(L, z_tiled, y_tiled, nullptr, alg_flag, eta0, comparator,
+                                     regret, cum_loss, comp_loss, x_last, flags, closed_out, stream);
+}
+
+int ocx_dev_simulate_alg_bits(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                              const uint64_t* y_bits, int alg_flag, double eta0,
+                              const double* comparator, double* regret, double* cum_loss,
+                              double* comp_loss, double* x_last, int flags, int32_t* closed_out,
+                              void* stream) {
     StreamDevice sd_(stream);
     if (int rc = check_layout(L)) return rc;
     if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL input buffer");
@@ -387,7 +418,8 @@ int ocx_dev_simulate_alg_ex(const ocx_layout* L, const double* z_tiled, const do
     // the two flags are one request: the kernel certifies every row and sub-gradient itself
     OCX_HIP(ocx_launch_alg(L, z_tiled, y_tiled, alg_flag != 0 ? 1 : 0, eta0, comparator, regret,
                            cum_loss, comp_loss, x_last, (hipStream_t)stream, nullptr, closed_out,
-                           (flags & (OCX_ALG_CLIPPED_ROWS | OCX_ALG_CLOSED_COMPARATOR)) ? 1 : 0));
+                           (flags & (OCX_ALG_CLIPPED_ROWS | OCX_ALG_CLOSED_COMPARATOR)) ? 1 : 0, 0,
+                           y_bits));
     return OCX_OK;
 }
 
@@ -2367,6 +2399,15 @@ int ocx_test_alg_range(const ocx_layout* L, const double* z_tiled, const double*
 int ocx_test_alg_pipe_persistent(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
                                  int ftl, double eta0, int onepass, int64_t nwaves, double* regret,
                                  double* cum, double* comp, int32_t* closed_out, void* stream) {
+    return ocx_test_alg_pipe_persistent_bits(L, z_tiled, y_tiled, nullptr, ftl, eta0, onepass,
+                                             nwaves, regret, cum, comp, closed_out, stream);
+}
+
+int ocx_test_alg_pipe_persistent_bits(const ocx_layout* L, const double* z_tiled,
+                                      const double* y_tiled, const uint64_t* y_bits, int ftl,
+                                      double eta0, int onepass, int64_t nwaves, double* regret,
+                                      double* cum, double* comp, int32_t* closed_out,
+                                      void* stream) {
     StreamDevice sd_(stream);
     if (int rc = check_layout(L)) return rc;
     if (!ocx_pipe_persistent_supported(L))
@@ -2378,7 +2419,8 @@ int ocx_test_alg_pipe_persistent(const ocx_layout* L, const double* z_tiled, con
         return fail(OCX_E_INVALID, "NULL buffer");
     const hipStream_t st = (hipStream_t)stream;
     const hipError_t e = ocx_launch_alg_pipe_persistent(L, z_tiled, y_tiled, ftl, eta0, regret, cum,
-                                                        comp, closed_out, onepass, nwaves, st);
+                                                        comp, closed_out, onepass, nwaves, st,
+                                                        y_bits);
     const hipError_t es = hipStreamSynchronize(st);
     OCX_HIP(e);
     OCX_HIP(es);

@@ -962,13 +962,24 @@ constexpr int kRows64 = 8;
 // overlapped pipeline; 0 otherwise), a multiple of the block's waves.
 // OV: 0, or the overlapped form's register budget in waves per SIMD (4: 128 VGPRs, beside an
 // FTRL wave at three generator waves per SIMD; 5: 96 VGPRs, four generator waves beside one)
+// bit i of x to bit 2i (x < 2^32)
+__device__ __forceinline__ uint64_t spread_bits32(uint64_t x) {
+    x = (x | (x << 16)) & 0x0000ffff0000ffffull;
+    x = (x | (x << 8)) & 0x00ff00ff00ff00ffull;
+    x = (x | (x << 4)) & 0x0f0f0f0f0f0f0f0full;
+    x = (x | (x << 2)) & 0x3333333333333333ull;
+    x = (x | (x << 1)) & 0x5555555555555555ull;
+    return x;
+}
+
 template <int MODE, int DF, bool LR = false, bool RAW = false, int OV = 0>
 __global__ __launch_bounds__(gen_block(DF, LR, OV), OV ? OV : OCX_GENW_MIN_WAVES_FOR(DF, LR)) void ocx_gen_wave_kernel(
     uint64_t base_seed, int64_t T_seed, int64_t run0, int64_t B, int64_t nseq, int64_t T,
     int d_arg, int P, int C, int64_t G, double* __restrict__ zt, double* __restrict__ ytl,
     const uint64_t* __restrict__ st_in, uint64_t* __restrict__ st_out,
     const uint64_t* __restrict__ lab_in, uint64_t* __restrict__ lab_out, int rb,
-    int64_t nwaves, int64_t b_off, int64_t t_off, int64_t nrows, int labels) {
+    int64_t nwaves, int64_t b_off, int64_t t_off, int64_t nrows, int labels,
+    uint64_t* __restrict__ ybits) {
     constexpr int kBlock = gen_block(DF, LR, OV);
     constexpr int kNW = kBlock / 64;
     // lane states in the round loop: the d = 64 row loop's FLAT rounds (see zig_round)
@@ -1076,6 +1087,9 @@ __global__ __launch_bounds__(gen_block(DF, LR, OV), OV ? OV : OCX_GENW_MIN_WAVES
                 for (int j = lane; j < Dp; j += 64) *zaddr(t, j) = 0.0;
             if (b >= B && !labels) continue;
             if (b >= B) {
+                if (ybits != nullptr)  // a padding sequence's label bits are 0
+                    for (int64_t k = lane; k < (T + 63) / 64; k += 64)
+                        ybits[(g * ((T + 63) / 64) + k) * S + s] = 0;
                 if (stage_y) {
                     // the block's label rounds (and barriers) with zeros for this sequence
                     for (int64_t tl = 0; tl < T; tl += 128) {
@@ -1416,6 +1430,27 @@ __global__ __launch_bounds__(gen_block(DF, LR, OV), OV ? OV : OCX_GENW_MIN_WAVES
             const ocx_u128 st = mul_add_u128(w.Ak, w.base, w.Dk);
             const uint64_t r = xsl_rr(st);
             const int64_t t0 = tl + 2 * lane;
+            if (ybits != nullptr) {
+                // The label-bit tile (include/ocx.h).  A wave is one stream and lane l drew labels
+                // tl + 2l (its draw's low half) and tl + 2l + 1 (the high half), so the two
+                // ballots interleaved are the round's 128 bits: lanes 0..31's one 64-step block's
+                // word, lanes 32..63's the next one's (fresh label streams only: tl is a multiple
+                // of 128).  The interleave runs on the scalar unit; bits at t >= T stay 0; one
+                // lane stores the words.  (Measured alternatives — each lane fetching its step's
+                // bit with a shuffle or a select before one ballot per word, and the words staged
+                // through LDS with the labels — were no faster: DESIGN.md §3.2.)
+                const uint64_t lo = __ballot((((uint32_t)r) >> 31) != 0);
+                const uint64_t hi = __ballot((((uint32_t)(r >> 32)) >> 31) != 0);
+                uint64_t w0 = spread_bits32(lo & 0xffffffffull) | (spread_bits32(hi & 0xffffffffull) << 1);
+                uint64_t w1 = spread_bits32(lo >> 32) | (spread_bits32(hi >> 32) << 1);
+                if (left < 64) w0 &= ((uint64_t)1 << left) - 1;
+                if (left < 128) w1 &= left > 64 ? ((uint64_t)1 << (left - 64)) - 1 : 0;
+                if (lane == 0) {
+                    uint64_t* wp = ybits + (g * ((T + 63) / 64) + (tl >> 6)) * S + s;
+                    wp[0] = w0;
+                    if (left > 64) wp[S] = w1;
+                }
+            }
             if (stage_y) {
                 ring[2 * lane] = (((uint32_t)r) >> 31) ? 1.0 : -1.0;
                 ring[2 * lane + 1] = (((uint32_t)(r >> 32)) >> 31) ? 1.0 : -1.0;
@@ -1455,7 +1490,8 @@ hipError_t launch_wave_df(uint64_t base_seed, int64_t T_seed, int64_t run0, int6
                           int64_t nseq, int64_t T, int64_t d, int P, int C, int64_t G, double* zt,
                           double* ytl, const uint64_t* st_in, uint64_t* st_out,
                           const uint64_t* lab_in, uint64_t* lab_out, hipStream_t st,
-                          int64_t t_off = 0, int64_t nrows = -1, int labels = 1) {
+                          int64_t t_off = 0, int64_t nrows = -1, int labels = 1,
+                          uint64_t* ybits = nullptr) {
     constexpr int kBlock = gen_block(DF, LR);
     const int rb = (MODE == 0) ? ring_doubles(d, DF, LR) : 0;
     const size_t lds =
@@ -1506,7 +1542,7 @@ hipError_t launch_wave_df(uint64_t base_seed, int64_t T_seed, int64_t run0, int6
     hipLaunchKernelGGL((ocx_gen_wave_kernel<MODE, DF, LR, RAW>), dim3(blocks), dim3(kBlock), lds, st,
                        base_seed, T_seed, run0, B, nseq, T, (int)d, P, C, G, zt, ytl, st_in,
                        st_out, lab_in, lab_out, rb, nwaves, (int64_t)0, t_off, nrows < 0 ? T : nrows,
-                       labels);
+                       labels, lab_in == nullptr ? ybits : nullptr);
     return hipGetLastError();
 }
 
@@ -1553,7 +1589,8 @@ OvGeom ov_geometry(int dev, int wps) {
 namespace {
 template <int DF>
 hipError_t launch_gen_range_df(const ocx_layout* L, uint64_t base_seed, int64_t run0, int64_t b_off,
-                               int64_t nseq, int wps, double* zt, double* ytl, hipStream_t st) {
+                               int64_t nseq, int wps, double* zt, double* ytl, hipStream_t st,
+                               uint64_t* ybits) {
     int dev = 0, cus = 256;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -1572,13 +1609,13 @@ hipError_t launch_gen_range_df(const ocx_layout* L, uint64_t base_seed, int64_t 
                            gm.lds, st, base_seed, L->T, run0, L->B, nseq, L->T, (int)L->d,
                            (int)L->P, (int)L->C, L->G, zt, ytl, (const uint64_t*)nullptr,
                            (uint64_t*)nullptr, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                           ring_doubles(DF, DF), nwaves, b_off, (int64_t)0, L->T, 1);
+                           ring_doubles(DF, DF), nwaves, b_off, (int64_t)0, L->T, 1, ybits);
     else
         hipLaunchKernelGGL((ocx_gen_wave_kernel<0, DF, false, false, 4>), dim3(blocks), dim3(256),
                            gm.lds, st, base_seed, L->T, run0, L->B, nseq, L->T, (int)L->d,
                            (int)L->P, (int)L->C, L->G, zt, ytl, (const uint64_t*)nullptr,
                            (uint64_t*)nullptr, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                           ring_doubles(DF, DF), nwaves, b_off, (int64_t)0, L->T, 1);
+                           ring_doubles(DF, DF), nwaves, b_off, (int64_t)0, L->T, 1, ybits);
     return hipGetLastError();
 }
 }  // namespace
@@ -1588,21 +1625,21 @@ hipError_t launch_gen_range_df(const ocx_layout* L, uint64_t base_seed, int64_t 
 // ov_geometry).
 hipError_t ocx_launch_gen_gT_range(const ocx_layout* L, uint64_t base_seed, int64_t run0,
                                    int64_t b_off, int64_t nseq, int wps, double* zt, double* ytl,
-                                   hipStream_t st) {
+                                   hipStream_t st, uint64_t* ybits) {
     if (nseq <= 0 || L->T == 0) return hipSuccess;
     if ((L->d != 64 && L->d != 32 && L->d != 16) || L->P * L->C != L->d || b_off % 4 || nseq % 4)
         return hipErrorInvalidValue;
     if (L->T * L->d >= ((int64_t)1 << 32)) return hipErrorInvalidValue;
-    if (L->d == 16) return launch_gen_range_df<16>(L, base_seed, run0, b_off, nseq, wps, zt, ytl, st);
-    if (L->d == 32) return launch_gen_range_df<32>(L, base_seed, run0, b_off, nseq, wps, zt, ytl, st);
-    return launch_gen_range_df<64>(L, base_seed, run0, b_off, nseq, wps, zt, ytl, st);
+    if (L->d == 16) return launch_gen_range_df<16>(L, base_seed, run0, b_off, nseq, wps, zt, ytl, st, ybits);
+    if (L->d == 32) return launch_gen_range_df<32>(L, base_seed, run0, b_off, nseq, wps, zt, ytl, st, ybits);
+    return launch_gen_range_df<64>(L, base_seed, run0, b_off, nseq, wps, zt, ytl, st, ybits);
 }
 
 // The few-stream (LR) form over sequences [b_off, b_off + nseq) of L, one wave per stream,
 // six waves per SIMD (80 VGPRs): a generator round for ocx_run_gen_rounds' tuning forms.
 hipError_t ocx_launch_gen_gT_range_lr(const ocx_layout* L, uint64_t base_seed, int64_t run0,
                                       int64_t b_off, int64_t nseq, double* zt, double* ytl,
-                                      hipStream_t st) {
+                                      hipStream_t st, uint64_t* ybits) {
     if (nseq <= 0 || L->T == 0) return hipSuccess;
     if (L->d != 64 || L->P * L->C != 64 || b_off % 4 || nseq % 4) return hipErrorInvalidValue;
     if (L->T * L->d >= ((int64_t)1 << 32)) return hipErrorInvalidValue;
@@ -1614,7 +1651,7 @@ hipError_t ocx_launch_gen_gT_range_lr(const ocx_layout* L, uint64_t base_seed, i
                        st, base_seed, L->T, run0, L->B, nseq, L->T, (int)L->d, (int)L->P,
                        (int)L->C, L->G, zt, ytl, (const uint64_t*)nullptr, (uint64_t*)nullptr,
                        (const uint64_t*)nullptr, (uint64_t*)nullptr, rb, (int64_t)blocks * (kBlock / 64),
-                       b_off, (int64_t)0, L->T, 1);
+                       b_off, (int64_t)0, L->T, 1, ybits);
     return hipGetLastError();
 }
 
@@ -1625,7 +1662,7 @@ hipError_t launch_wave(uint64_t base_seed, int64_t T_seed, int64_t run0, int64_t
                        int64_t T, int64_t d, int P, int C, int64_t G, double* zt, double* ytl,
                        const uint64_t* st_in, uint64_t* st_out, const uint64_t* lab_in,
                        uint64_t* lab_out, hipStream_t st, int64_t t_off = 0, int64_t nrows = -1,
-                       int labels = 1) {
+                       int labels = 1, uint64_t* ybits = nullptr) {
     // the kernel counts a sequence's normals in 32 bits
     if ((MODE == 0 ? T : T_seed) * d >= ((int64_t)1 << 32)) return hipErrorInvalidValue;
     if (d == 64 && (MODE == 1 || (int64_t)P * C == 64)) {
@@ -1662,9 +1699,9 @@ hipError_t launch_wave(uint64_t base_seed, int64_t T_seed, int64_t run0, int64_t
         if (MODE == 0 && lr)
             return launch_wave_df<MODE, 64, true>(base_seed, T_seed, run0, B, nseq, T, d, P, C, G,
                                                   zt, ytl, st_in, st_out, lab_in, lab_out, st,
-                                                  t_off, nrows, labels);
+                                                  t_off, nrows, labels, ybits);
         return launch_wave_df<MODE, 64>(base_seed, T_seed, run0, B, nseq, T, d, P, C, G, zt, ytl,
-                                        st_in, st_out, lab_in, lab_out, st, t_off, nrows, labels);
+                                        st_in, st_out, lab_in, lab_out, st, t_off, nrows, labels, ybits);
     }
     // d = 16 / 32 rows that fill their lanes (P·C = d): the d = 64 loop's form over 512-normal
     // batches (OCX_GEN_SMALL=0: the generic loop, tuning)
@@ -1674,17 +1711,17 @@ hipError_t launch_wave(uint64_t base_seed, int64_t T_seed, int64_t run0, int64_t
             if (d == 16)
                 return launch_wave_df<MODE, 16>(base_seed, T_seed, run0, B, nseq, T, d, P, C, G, zt,
                                                 ytl, st_in, st_out, lab_in, lab_out, st, t_off, nrows,
-                                                labels);
+                                                labels, ybits);
             return launch_wave_df<MODE, 32>(base_seed, T_seed, run0, B, nseq, T, d, P, C, G, zt, ytl,
-                                            st_in, st_out, lab_in, lab_out, st, t_off, nrows, labels);
+                                            st_in, st_out, lab_in, lab_out, st, t_off, nrows, labels, ybits);
         }
     }
     if (MODE == 0 && d == 1024 && (int64_t)P * C == 1024 && P <= 64)
         return launch_wave_df<MODE, 1024>(base_seed, T_seed, run0, B, nseq, T, d, P, C, G, zt,
                                           ytl, st_in, st_out, lab_in, lab_out, st, t_off, nrows,
-                                          labels);
+                                          labels, ybits);
     return launch_wave_df<MODE, 0>(base_seed, T_seed, run0, B, nseq, T, d, P, C, G, zt, ytl,
-                                   st_in, st_out, lab_in, lab_out, st, t_off, nrows, labels);
+                                   st_in, st_out, lab_in, lab_out, st, t_off, nrows, labels, ybits);
 }
 
 }  // namespace
@@ -1715,7 +1752,7 @@ int64_t ocx_gen_resident_waves(int64_t d, int dev) {
 }
 
 hipError_t ocx_launch_gen_gT(const ocx_layout* L, uint64_t base_seed, int64_t run0, double* zt,
-                             double* ytl, hipStream_t st) {
+                             double* ytl, hipStream_t st, uint64_t* ybits) {
     const int64_t nseq = L->G * L->S;
     if (nseq == 0 || L->T == 0) return hipSuccess;
     // d = 64 batches of four or more generator rounds: one round per launch over two streams
@@ -1724,9 +1761,9 @@ hipError_t ocx_launch_gen_gT(const ocx_layout* L, uint64_t base_seed, int64_t ru
     const char* gr = std::getenv("OCX_GEN_ROUNDS");
     if ((!gr || std::atoi(gr) != 0) && L->d == 64 && ocx_pipeline_supported(L) &&
         ocx_pipeline_worth(L, 4) && ocx_stream_fork_ok(st))
-        return ocx_run_gen_rounds(L, base_seed, run0, zt, ytl, st);
+        return ocx_run_gen_rounds(L, base_seed, run0, zt, ytl, st, ybits);
     return launch_wave<0>(base_seed, L->T, run0, L->B, nseq, L->T, L->d, L->P, L->C, L->G, zt,
-                          ytl, nullptr, nullptr, nullptr, nullptr, st);
+                          ytl, nullptr, nullptr, nullptr, nullptr, st, 0, -1, 1, ybits);
 }
 
 hipError_t ocx_launch_gen_gT_raw(const ocx_layout* L, uint64_t base_seed, int64_t run0, double* zt,

@@ -139,7 +139,7 @@ bool ocx_pipeline_worth(const ocx_layout* L, int wps) {
 // before the next starts, joined back on `st`.  The normals and labels are the one-launch
 // generator's, bit for bit (the same kernel body).
 hipError_t ocx_run_gen_rounds(const ocx_layout* L, uint64_t base_seed, int64_t run0, double* zt,
-                              double* yt, hipStream_t st) {
+                              double* yt, hipStream_t st, uint64_t* ybits) {
     // The round's form (OCX_GEN_ROUNDS_FORM overrides, tuning): "lr6", the default, the
     // few-stream form (80 VGPRs) at six waves per SIMD; "ov5" / "ov4" the 96-VGPR four-wave-
     // block form at five / four.  32 768 x 1e4 x 64: 49.7 / 50.2 / 52.3 ms, one launch 58.1
@@ -165,9 +165,9 @@ hipError_t ocx_run_gen_rounds(const ocx_layout* L, uint64_t base_seed, int64_t r
     int64_t j = 0;
     for (int64_t b0 = 0; b0 < Bp; b0 += sub, ++j)
         OCX_PIPE_TRY(lr6 ? ocx_launch_gen_gT_range_lr(L, base_seed, run0, b0, std::min(sub, Bp - b0),
-                                                      zt, yt, (j & 1) ? c.gen2 : st)
+                                                      zt, yt, (j & 1) ? c.gen2 : st, ybits)
                          : ocx_launch_gen_gT_range(L, base_seed, run0, b0, std::min(sub, Bp - b0),
-                                                   wps, zt, yt, (j & 1) ? c.gen2 : st));
+                                                   wps, zt, yt, (j & 1) ? c.gen2 : st, ybits));
     OCX_PIPE_TRY(hipEventRecord(c.join_gen2, c.gen2));
     OCX_PIPE_TRY(hipStreamWaitEvent(st, c.join_gen2, 0));
     return hipSuccess;

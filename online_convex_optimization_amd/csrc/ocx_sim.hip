@@ -452,6 +452,50 @@ __global__ void ocx_pack_y_kernel(const double* __restrict__ y, double* __restri
     }
 }
 
+// The label-bit tile of a row-major y (include/ocx.h): word o = (g*KB + k)*S + s, bit i set
+// where y[g*S + s][64k + i] == +1.0; bits at t >= T and of padding sequences are 0.  *flag is
+// raised if any label of a real sequence is not exactly ±1.0 (the tile is then not to be used).
+__global__ void ocx_pack_ybits_kernel(const double* __restrict__ y, uint64_t* __restrict__ yb,
+                                      int64_t B, int64_t T, int S, int64_t KB, int64_t total,
+                                      int* __restrict__ flag) {
+    bool odd = false;
+    for (int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; o < total;
+         o += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t gk = o / S;
+        const int s = (int)(o - gk * S);
+        const int64_t g = gk / KB, k = gk - g * KB;
+        const int64_t b = g * S + s;
+        uint64_t w = 0;
+        if (b < B) {
+            const int64_t t0 = k * 64;
+            const int n = (int)(T - t0 < 64 ? T - t0 : 64);
+            const double* __restrict__ row = y + b * T + t0;
+            for (int i = 0; i < n; ++i) {
+                const double v = row[i];
+                if (v == 1.0) w |= (uint64_t)1 << i;
+                else if (v != -1.0) odd = true;
+            }
+        }
+        yb[o] = w;
+    }
+    if (odd) atomicOr(flag, 1);
+}
+
+int64_t ocx_label_bits_words_of(const ocx_layout* L) { return L->G * ((L->T + 63) / 64) * L->S; }
+
+hipError_t ocx_launch_pack_ybits(const ocx_layout* L, const double* y, uint64_t* yb, int* flag,
+                                 hipStream_t st) {
+    hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), st);
+    if (e != hipSuccess) return e;
+    const int64_t n = ocx_label_bits_words_of(L);
+    if (n > 0) {
+        const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 65536);
+        hipLaunchKernelGGL(ocx_pack_ybits_kernel, dim3(grid), dim3(256), 0, st, y, yb, L->B, L->T,
+                           (int)L->S, (L->T + 63) / 64, n, flag);
+    }
+    return hipGetLastError();
+}
+
 // max over runs starting from 0.0 with `reg > max` (fast_algorithms.py:228, :242-243)
 __global__ void ocx_max_kernel(const double* __restrict__ r, int64_t B, double* __restrict__ out) {
     __shared__ double sm[OCX_BLOCK];
@@ -542,7 +586,7 @@ bool ocx_supported_C(int C) {
 hipError_t ocx_launch_alg(const ocx_layout* L, const double* zt, const double* yt, int algo,
                           double eta0, const double* cmp, double* reg, double* cum, double* comp,
                           double* xl, hipStream_t st, double* cmp_out, int* regime, int onepass,
-                          int norm) {
+                          int norm, const uint64_t* yb) {
     if (L->G == 0) return hipSuccess;
     // butterfly layouts: the pipelined step (ocx_alg_pipe.hip) unless an input comparator,
     // x_last or the comparator action is asked for (OCX_ALG_NO_PIPE=1: the plain kernel,
@@ -552,7 +596,7 @@ hipError_t ocx_launch_alg(const ocx_layout* L, const double* zt, const double* y
         return e && std::atoi(e) != 0;
     }();
     if ((algo == 0 || algo == 1) && !cmp && !xl && !cmp_out && !no_pipe && ocx_pipe_supported(L))
-        return ocx_launch_alg_pipe(L, zt, yt, algo, eta0, reg, cum, comp, regime, onepass, st);
+        return ocx_launch_alg_pipe(L, zt, yt, algo, eta0, reg, cum, comp, regime, onepass, st, yb);
     OCX_DISPATCH(launch_alg_cp, L, zt, yt, algo, eta0, cmp, reg, cum, comp, xl, cmp_out, regime,
                  onepass, norm, st)
 }

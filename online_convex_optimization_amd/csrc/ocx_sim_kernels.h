@@ -12,20 +12,30 @@ bool ocx_supported_C(int C);
 hipError_t ocx_launch_alg(const ocx_layout* L, const double* zt, const double* yt, int algo,
                           double eta0, const double* cmp, double* reg, double* cum, double* comp,
                           double* xl, hipStream_t st, double* cmp_out = nullptr,
-                          int* regime = nullptr, int onepass = 0, int norm = 0);
+                          int* regime = nullptr, int onepass = 0, int norm = 0,
+                          const uint64_t* yb = nullptr);
+// The label-bit tile (include/ocx.h, ocx_label_bits_words): yb, where a launcher takes it, is
+// nullable and must describe the same labels as yt, every label of a real sequence ±1.  The
+// instances of the pipelined step that read it: ocx_alg_pipe.hip.
+int64_t ocx_label_bits_words_of(const ocx_layout* L);
+// the tile of a row-major y [B][T]; *flag (device) = 1 if a real label is not exactly ±1
+hipError_t ocx_launch_pack_ybits(const ocx_layout* L, const double* y, uint64_t* yb, int* flag,
+                                 hipStream_t st);
 // FTRL / FTL for butterfly layouts (chain = 0, P >= 2, C <= 32) with the step's dependency
 // chain cut short (ocx_alg_pipe.hip); no comparator input, x_last or comparator output
 bool ocx_pipe_supported(const ocx_layout* L);
 hipError_t ocx_launch_alg_pipe(const ocx_layout* L, const double* zt, const double* yt, int ftl,
                                double eta0, double* reg, double* cum, double* comp,
-                               int* closed_out, int onepass, hipStream_t st);
+                               int* closed_out, int onepass, hipStream_t st,
+                               const uint64_t* yb = nullptr);
 // its persistent instance (a batch of more groups than are resident at once: each wave loops
 // over its share) with `nwaves` waves, whatever the batch's size; the layouts that have one
 bool ocx_pipe_persistent_supported(const ocx_layout* L);
 hipError_t ocx_launch_alg_pipe_persistent(const ocx_layout* L, const double* zt, const double* yt,
                                           int ftl, double eta0, double* reg, double* cum,
                                           double* comp, int* closed_out, int onepass,
-                                          int64_t nwaves, hipStream_t st);
+                                          int64_t nwaves, hipStream_t st,
+                                          const uint64_t* yb = nullptr);
 // Regret curves (ocx_alg_curve.hip): FTRL / FTL observed at the K checkpoints ck (device,
 // strictly increasing in [0, T]) in one pass; outputs [B][K] (each nullable).  The curve form
 // of the pipelined kernel where ocx_pipe_supported(L), of the plain kernel otherwise; then
@@ -83,7 +93,7 @@ hipError_t ocx_launch_alg_pipe_chunk(const ocx_layout* L, const double* zt, cons
 // (wps >= 4: the 96-VGPR form, which spills a little; below: the 128-VGPR form)
 hipError_t ocx_launch_gen_gT_range(const ocx_layout* L, uint64_t base_seed, int64_t run0,
                                    int64_t b_off, int64_t nseq, int wps, double* zt, double* ytl,
-                                   hipStream_t st);
+                                   hipStream_t st, uint64_t* ybits = nullptr);
 // generation overlapped with FTRL (ocx_pipeline.hip): nbatch batches of L->B runs from run0,
 // regret = the last batch's; gmax (nullable, device) max-folds g(T) over every batch
 bool ocx_pipeline_supported(const ocx_layout* L);
@@ -92,10 +102,10 @@ bool ocx_pipeline_worth(const ocx_layout* L, int wps);
 bool ocx_stream_fork_ok(hipStream_t st);
 hipError_t ocx_launch_gen_gT_range_lr(const ocx_layout* L, uint64_t base_seed, int64_t run0,
                                       int64_t b_off, int64_t nseq, double* zt, double* ytl,
-                                      hipStream_t st);
+                                      hipStream_t st, uint64_t* ybits = nullptr);
 // generation alone in rounds over two streams (ocx_pipeline.hip)
 hipError_t ocx_run_gen_rounds(const ocx_layout* L, uint64_t base_seed, int64_t run0, double* zt,
-                              double* yt, hipStream_t st);
+                              double* yt, hipStream_t st, uint64_t* ybits = nullptr);
 hipError_t ocx_run_gen_sim_pipelined(const ocx_layout* L, uint64_t base_seed, int64_t run0,
                                      int64_t nbatch, double* zt, double* yt, double eta0,
                                      double* regret, int onepass, unsigned long long* gmax,
@@ -210,8 +220,9 @@ int64_t ocx_gen_resident_waves(int64_t d, int dev);  // streams the generator ru
 hipError_t ocx_launch_alg_range(const ocx_layout* L, const double* zt, const double* yt,
                                 double eta0, double* reg, int onepass, int64_t g0, int64_t gn,
                                 unsigned long long* gmax, hipStream_t st);
+// ybits (nullable): the label-bit tile, filled beside ytl
 hipError_t ocx_launch_gen_gT(const ocx_layout* L, uint64_t base_seed, int64_t run0, double* zt,
-                             double* ytl, hipStream_t st);
+                             double* ytl, hipStream_t st, uint64_t* ybits = nullptr);
 // the g(T) sampler's normals unclipped (the float32 twin clips them itself)
 hipError_t ocx_launch_gen_gT_raw(const ocx_layout* L, uint64_t base_seed, int64_t run0, double* zt,
                                  double* ytl, hipStream_t st);

@@ -881,12 +881,31 @@ def gT_sweep(T_grid: Sequence[int], runs: int, *, base_seed: int = 0, d: int = 5
 # Device-resident batches (torch tensors as HBM buffers)
 # ---------------------------------------------------------------------------
 
+def tiled_rows(z_tiled, y_tiled, L, seqs):
+    """z [n, T, d] and y [n, T] (row-major, contiguous) of the sequences ``seqs`` (int64 tensor
+    of batch indices), gathered out of tiled tensors of layout L (include/ocx.h ocx_layout:
+    z_tiled[((k*G + g)*T + t)*128 + L*2 + e], y_tiled[(g*T + t)*S + s]).  Reads only."""
+    K, G, T, S, P = L.C // 2, L.G, L.T, L.S, L.P
+    g, s = seqs // S, seqs % S
+    z5 = z_tiled[:K * G * T * 128].view(K, G, T, S, P, 2)
+    zs = z5[:, g, :, s, :, :]                      # [n, K, T, P, 2]
+    zs = zs.permute(0, 2, 3, 1, 4).reshape(seqs.numel(), T, P * L.C)[:, :, :L.d]
+    ys = y_tiled[:G * T * S].view(G, T, S)[g, :, s]  # [n, T]
+    return zs.contiguous(), ys.contiguous()
+
+
 class DeviceBatch:
     """B sequences of T steps in d dimensions, resident in HBM in the tiled layout.
 
     ``stream`` is a torch.cuda.Stream (default: the current stream); every kernel
     of this object is launched on it, so torch events recorded on that stream
-    bracket the HIP kernels exactly."""
+    bracket the HIP kernels exactly.
+
+    Beside the label tile ``y`` the batch owns the label-bit tile (include/ocx.h): one bit per
+    label, filled by generate_gT and pack, and read by simulate_alg instead
+    of ``y``'s doubles while it is known to describe them (``label_bits_valid``).  ``y`` is a
+    property: any access from outside may write labels in place, so it marks the bits invalid
+    until the next producer call."""
 
     def __init__(self, B: int, T: int, d: int, *, lanes_per_seq: int = LANES_BEST, device: int = 0,
                  stream=None):
@@ -902,11 +921,35 @@ class DeviceBatch:
             self.stream = stream if stream is not None else torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             self.z = torch.empty(max(self.L.z_elems, 1), dtype=torch.float64, device=self.device)
-            self.y = torch.empty(max(self.L.y_elems, 1), dtype=torch.float64, device=self.device)
+            self._y = torch.empty(max(self.L.y_elems, 1), dtype=torch.float64, device=self.device)
+            nbits = self.L.G * ((self.L.T + 63) // 64) * self.L.S
+            self._ybits = torch.zeros(max(nbits, 1), dtype=torch.int64, device=self.device)
+            self._bits_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
             self.regret = torch.zeros(max(B, 1), dtype=torch.float64, device=self.device)
             self.cum = torch.zeros_like(self.regret)
             self.comp = torch.zeros_like(self.regret)
         self.cum_exact = None  # allocated by ftrl_vs_exact
+        # whether the label-bit tile describes y (set by the producers, cleared by any access
+        # to y from outside)
+        self._bits_state = "invalid"
+
+    @property
+    def y(self):
+        """The label tile (y_tiled).  Handing it out marks the label bits invalid: the caller
+        may write labels in place."""
+        self._bits_state = "invalid"
+        return self._y
+
+    @y.setter
+    def y(self, value):
+        self._bits_state = "invalid"
+        self._y = value
+
+    @property
+    def label_bits_valid(self) -> bool:
+        """Whether the label-bit tile describes ``y`` (every label of a real sequence ±1), so
+        simulate_alg may read it.  Host state only: no device read, no synchronisation."""
+        return self._bits_state == "valid"
 
     @property
     def _sp(self):
@@ -939,9 +982,11 @@ class DeviceBatch:
 
     def generate_gT(self, base_seed: int = 0, run0: int = 0):
         """Fill z/y with _rng(base_seed, T, run0 + b) sequences (on device)."""
-        self._call("ocx_dev_gen_gT", self._lp(), int(base_seed), int(run0), self.z.data_ptr(),
-                  self.y.data_ptr(), self._sp)
+        self._bits_state = "invalid"
+        self._call("ocx_dev_gen_gT_bits", self._lp(), int(base_seed), int(run0), self.z.data_ptr(),
+                  self._y.data_ptr(), self._ybits.data_ptr(), self._sp)
         self.rows_clipped = True
+        self._bits_state = "valid"
         return self
 
     FAMILIES = {"iid": 1, "massart": 2, "flip": 3, "switching": 4}
@@ -962,15 +1007,18 @@ class DeviceBatch:
             if rs.numel() != self.L.B or si.numel() != self.L.B:
                 raise ValueError("need one run seed and one stream id per sequence")
         self.rows_clipped = False
+        self._bits_state = "invalid"
         self._call("ocx_dev_gen_family", self._lp(), fam,
                   rs.data_ptr() if rs is not None else None,
                   si.data_ptr() if si is not None else None, float(p), int(block_len),
-                  self.z.data_ptr(), self.y.data_ptr(), self._sp)
+                  self.z.data_ptr(), self._y.data_ptr(), self._sp)
         self._keep_seeds = self._hold(rs, si)
         return self
 
     def pack(self, z, y):
-        """Copy host/device arrays z [B,T,d], y [B,T] into the tiled layout."""
+        """Copy host/device arrays z [B,T,d], y [B,T] into the tiled layout, and the labels into
+        the label-bit tile, which is kept only if every label is exactly ±1 (a device flag,
+        read back here: pack synchronises the batch's stream)."""
         torch = self.torch
         with self._on_stream():
             zt = torch.as_tensor(np.ascontiguousarray(z, dtype=np.float64)
@@ -982,8 +1030,15 @@ class DeviceBatch:
         if tuple(zt.shape) != (self.L.B, self.L.T, self.L.d) or tuple(yt.shape) != (self.L.B, self.L.T):
             raise ValueError("z/y shape does not match the batch")
         self.rows_clipped = False
-        self._call("ocx_dev_pack", self._lp(), zt.data_ptr(), yt.data_ptr(), self.z.data_ptr(),
-                  self.y.data_ptr(), self._sp)
+        self._bits_state = "invalid"
+        self._call("ocx_dev_pack_bits", self._lp(), zt.data_ptr(), yt.data_ptr(), self.z.data_ptr(),
+                  self._y.data_ptr(), self._ybits.data_ptr(), self._bits_flag.data_ptr(), self._sp)
+        # kept only if the kernel's flag stayed clear.  The flag is read here, on this batch's
+        # stream (the one its kernel ran on), so pack synchronises that stream — it already waits
+        # for its host-to-device copies — and simulate_alg never does.
+        with self._on_stream():
+            not_unit = int(self._bits_flag.item())
+        self._bits_state = "invalid" if not_unit else "valid"
         self._keep = self._hold(zt, yt)
         return self
 
@@ -999,14 +1054,19 @@ class DeviceBatch:
         safe on any data: sequences that fail the check stream the second pass and are
         bit-identical to ``closed_comparator=False``.
         ``closed_out`` ([B] int32 device tensor, optional) receives 1 per sequence that took
-        the closed form, 0 where the kernel streamed the second pass."""
+        the closed form, 0 where the kernel streamed the second pass.
+        While ``label_bits_valid`` the pipelined kernel's instances built for it read the
+        label-bit tile instead of ``y`` (ocx_dev_simulate_alg_bits): the same results bit for
+        bit; OCX_LABEL_BITS=0 in the environment keeps every launch on ``y``."""
         cp = comparator.data_ptr() if comparator is not None else None
         xp = x_last.data_ptr() if x_last is not None else None
         if closed_comparator is None:
             closed_comparator = not self.exact and comparator is None
         flags = _lib.OCX_ALG_CLIPPED_ROWS if closed_comparator else 0
-        self._call("ocx_dev_simulate_alg_ex", self._lp(), self.z.data_ptr(), self.y.data_ptr(),
-                  int(alg_flag), float(eta0), cp, self.regret.data_ptr(), self.cum.data_ptr(),
+        bits = (self._ybits.data_ptr() if comparator is None and x_last is None
+                and self.label_bits_valid else None)
+        self._call("ocx_dev_simulate_alg_bits", self._lp(), self.z.data_ptr(), self._y.data_ptr(),
+                  bits, int(alg_flag), float(eta0), cp, self.regret.data_ptr(), self.cum.data_ptr(),
                   self.comp.data_ptr(), xp, flags,
                   closed_out.data_ptr() if closed_out is not None else None, self._sp)
         return self.regret
@@ -1035,7 +1095,7 @@ class DeviceBatch:
                    for k in ("regret", "cum", "comp")}
             out["closed"] = torch.zeros((B, K), dtype=torch.int32, device=self.device)
             ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self.device)
-        self._call("ocx_dev_simulate_alg_curve", self._lp(), self.z.data_ptr(), self.y.data_ptr(),
+        self._call("ocx_dev_simulate_alg_curve", self._lp(), self.z.data_ptr(), self._y.data_ptr(),
                    int(alg_flag), float(eta0), ckd.data_ptr() if K else None, K,
                    out["regret"].data_ptr(), out["cum"].data_ptr(), out["comp"].data_ptr(),
                    out["closed"].data_ptr(), flags, ws.data_ptr(), ws.numel() * 8, self._sp)
@@ -1061,7 +1121,7 @@ class DeviceBatch:
             out = {k: torch.zeros((B, M), dtype=torch.float64, device=self.device)
                    for k in ("regret", "cum", "comp")}
             out["closed"] = torch.zeros((B, M), dtype=torch.int32, device=self.device)
-        args = (self._lp(), self.z.data_ptr(), self.y.data_ptr(), ptr(et), M,
+        args = (self._lp(), self.z.data_ptr(), self._y.data_ptr(), ptr(et), M,
                 out["regret"].data_ptr(), out["cum"].data_ptr(), out["comp"].data_ptr(),
                 out["closed"].data_ptr(), flags)
         if _group is None:
@@ -1102,7 +1162,7 @@ class DeviceBatch:
                    for k in ("regret", "cum", "comp")}
             out["closed"] = torch.zeros((B, M, K), dtype=torch.int32, device=self.device)
             ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self.device)
-        head = (self._lp(), self.z.data_ptr(), self.y.data_ptr(), ptr(et), M,
+        head = (self._lp(), self.z.data_ptr(), self._y.data_ptr(), ptr(et), M,
                 ckd.data_ptr() if K else None, K, out["regret"].data_ptr(),
                 out["cum"].data_ptr(), out["comp"].data_ptr(), out["closed"].data_ptr(), flags)
         tail = (ws.data_ptr(), ws.numel() * 8, self._sp)
@@ -1135,7 +1195,7 @@ class DeviceBatch:
             closed_comparator = not self.exact
         flags = ((_lib.OCX_SMART_CLOSED_PREFIX if closed_prefix else 0) |
                  (_lib.OCX_ALG_CLOSED_COMPARATOR if closed_comparator else 0))
-        self._call("ocx_dev_simulate_smart_ex", self._lp(), self.z.data_ptr(), self.y.data_ptr(),
+        self._call("ocx_dev_simulate_smart_ex", self._lp(), self.z.data_ptr(), self._y.data_ptr(),
                   th.data_ptr(), float(eta0), self.regret.data_ptr(), sp, flags,
                   stats.data_ptr() if stats is not None else None, self._sp)
         self._keep_th = self._hold(th)
@@ -1180,7 +1240,7 @@ class DeviceBatch:
             th = torch.as_tensor(tha).to(self.device)
             out = {"regret": torch.zeros((B, M), dtype=torch.float64, device=self.device),
                    "switch_step": torch.full((B, M), -1, dtype=torch.int64, device=self.device)}
-        args = (self._lp(), self.z.data_ptr(), self.y.data_ptr(), th.data_ptr() if B * M else None,
+        args = (self._lp(), self.z.data_ptr(), self._y.data_ptr(), th.data_ptr() if B * M else None,
                 M, float(eta0), out["regret"].data_ptr() if B * M else None,
                 out["switch_step"].data_ptr() if B * M else None, flags,
                 stats.data_ptr() if stats is not None else None)
@@ -1231,7 +1291,7 @@ class DeviceBatch:
             th = torch.as_tensor(tha).to(self.device)
             out = {"regret": torch.zeros((B, K), dtype=torch.float64, device=self.device),
                    "switch_step": torch.full((B, K), -1, dtype=torch.int64, device=self.device)}
-        args = (self._lp(), self.z.data_ptr(), self.y.data_ptr(),
+        args = (self._lp(), self.z.data_ptr(), self._y.data_ptr(),
                 hz.ctypes.data_as(_lib.c_i64p), th.data_ptr() if B * K else None, K, float(eta0),
                 out["regret"].data_ptr() if B * K else None,
                 out["switch_step"].data_ptr() if B * K else None, flags,
@@ -1290,7 +1350,7 @@ class DeviceBatch:
             out = {"regret": torch.zeros((B, M, K), dtype=torch.float64, device=self.device),
                    "switch_step": torch.full((B, M, K), -1, dtype=torch.int64,
                                              device=self.device)}
-        args = (self._lp(), self.z.data_ptr(), self.y.data_ptr(), th.data_ptr() if B * M else None,
+        args = (self._lp(), self.z.data_ptr(), self._y.data_ptr(), th.data_ptr() if B * M else None,
                 M, ckd.data_ptr() if K else None, K, float(eta0),
                 out["regret"].data_ptr() if n else None,
                 out["switch_step"].data_ptr() if n else None,
@@ -1342,7 +1402,7 @@ class DeviceBatch:
             if int(algo) == 2:
                 th = torch.as_tensor(np.broadcast_to(np.asarray(thresh, dtype=np.float64),
                                                      (self.L.B,)).copy()).to(self.device)
-        self._call("ocx_dev_twin32", self._lp(), self.z.data_ptr(), self.y.data_ptr(), int(algo),
+        self._call("ocx_dev_twin32", self._lp(), self.z.data_ptr(), self._y.data_ptr(), int(algo),
                   float(eta0), th.data_ptr() if th is not None else None, res.data_ptr(), None,
                   None, None, self._sp)
         if th is not None:
@@ -1375,7 +1435,7 @@ class DeviceBatch:
                    "comp": torch.zeros((B, K), dtype=torch.float32, device=self.device),
                    "switch_step": torch.full((B, K), -1, dtype=torch.int64, device=self.device)}
         some = B * K > 0
-        args = (self._lp(), self.z.data_ptr(), self.y.data_ptr(), K,
+        args = (self._lp(), self.z.data_ptr(), self._y.data_ptr(), K,
                 hz.ctypes.data_as(_lib.c_i64p), al.ctypes.data_as(_lib.c_i32p), float(eta0),
                 th.data_ptr() if th is not None and some else None,
                 *(out[k].data_ptr() if some else None
@@ -1422,7 +1482,7 @@ class DeviceBatch:
         if regime is None:
             with self._on_stream():
                 regime = torch.zeros(max(self.L.B, 1), dtype=torch.int32, device=self.device)
-        self._call("ocx_dev_ftl_exact", self._lp(), self.z.data_ptr(), self.y.data_ptr(),
+        self._call("ocx_dev_ftl_exact", self._lp(), self.z.data_ptr(), self._y.data_ptr(),
                   _norm_code(norm),
                   self.cum.data_ptr(), self.comp.data_ptr(),
                   cmp_action.data_ptr() if cmp_action is not None else None,
@@ -1452,7 +1512,7 @@ class DeviceBatch:
             # OCX_LANES_BEST: chained totals leave this kernel latency-bound (43 vs 28 ms at
             # 32768 x 1e4 x 64, profiles/r02_fused_exact_lanes.jsonl): butterfly sums instead
             flags |= _lib.OCX_ALG_TREE_SUMS
-        self._call("ocx_dev_ftrl_vs_exact_ex", self._lp(), self.z.data_ptr(), self.y.data_ptr(),
+        self._call("ocx_dev_ftrl_vs_exact_ex", self._lp(), self.z.data_ptr(), self._y.data_ptr(),
                   float(eta0), self.cum.data_ptr(), self.cum_exact.data_ptr(),
                   self.comp.data_ptr(), comp_ftl.data_ptr() if comp_ftl is not None else None,
                   cmp_action.data_ptr() if cmp_action is not None else None, regime.data_ptr(),
@@ -1477,7 +1537,7 @@ class DeviceBatch:
                 out[k] = torch.zeros((max(B, 1), NP), dtype=torch.float64, device=self.device)
             out["info"] = torch.zeros((max(B, 1), NP), dtype=torch.int32, device=self.device)
         self._call("ocx_dev_exact_ball_solve_tiled", self._lp(), self.z.data_ptr(),
-                  self.y.data_ptr(), _norm_code(norm), int(bool(all_prefixes)),
+                  self._y.data_ptr(), _norm_code(norm), int(bool(all_prefixes)),
                   out["actions"].data_ptr(), out["obj"].data_ptr(), out["gap"].data_ptr(),
                   out["step_loss"].data_ptr(), out["info"].data_ptr(), self._sp)
         return out
@@ -1497,7 +1557,7 @@ class DeviceBatch:
                 return regime
             # only the sequences outside the regime: their rows out of the tile, row-major
             bad = torch.nonzero(~ok).flatten()
-            zb, yb = self.rows_of(bad)
+            zb, yb = tiled_rows(self.z, self._y, self.L, bad)  # read only: the bits stay valid
             nb = int(bad.numel())
             res = {"actions": torch.zeros((nb, T + 1, d), dtype=torch.float64, device=self.device)}
             for k in ("obj", "gap", "step_loss"):
@@ -1556,7 +1616,7 @@ class DeviceBatch:
             ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self.device)
         if K and B:
             self._call("ocx_dev_ftrl_vs_exact_curve", self._lp(), self.z.data_ptr(),
-                       self.y.data_ptr(), float(eta0), ckd.data_ptr(), K,
+                       self._y.data_ptr(), float(eta0), ckd.data_ptr(), K,
                        out["cum_ftrl"].data_ptr(), out["cum_exact"].data_ptr(),
                        out["comp"].data_ptr(),
                        out["comp_ftl"].data_ptr() if with_ftl_comparator else None,
@@ -1610,7 +1670,7 @@ class DeviceBatch:
                 return
             bad = torch.nonzero(out_of.any(dim=1)).flatten()
             nb, Tm = int(bad.numel()), int(ck[-1])
-            zb, yb = self.rows_of(bad)
+            zb, yb = tiled_rows(self.z, self._y, self.L, bad)  # read only: the bits stay valid
             zb, yb = zb[:, :Tm].contiguous(), yb[:, :Tm].contiguous()
             res = {"actions": torch.zeros((nb, Tm + 1, d), dtype=torch.float64,
                                           device=self.device)}
@@ -1677,7 +1737,7 @@ class DeviceBatch:
             ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self.device)
         if K and B and M:
             self._call("ocx_dev_ftrl_vs_exact_curve_etas", self._lp(), self.z.data_ptr(),
-                       self.y.data_ptr(), ptr(et), M, ckd.data_ptr(), K,
+                       self._y.data_ptr(), ptr(et), M, ckd.data_ptr(), K,
                        out["cum_ftrl"].data_ptr(), out["cum_exact"].data_ptr(),
                        out["comp"].data_ptr(),
                        out["comp_ftl"].data_ptr() if with_ftl_comparator else None,
@@ -1741,15 +1801,10 @@ class DeviceBatch:
     def rows_of(self, seqs):
         """z [n, T, d] and y [n, T] (device, row-major, contiguous) of the sequences ``seqs``
         (device int64 tensor of batch indices), gathered out of the tiled layout
-        (include/ocx.h ocx_layout: z_tiled[((k*G + g)*T + t)*128 + L*2 + e])."""
-        L = self.L
-        K, G, T, S, P = L.C // 2, L.G, L.T, L.S, L.P
-        g, s = seqs // S, seqs % S
-        z5 = self.z[:K * G * T * 128].view(K, G, T, S, P, 2)
-        zs = z5[:, g, :, s, :, :]                      # [n, K, T, P, 2]
-        zs = zs.permute(0, 2, 3, 1, 4).reshape(seqs.numel(), T, P * L.C)[:, :, :L.d]
-        ys = self.y[:G * T * S].view(G, T, S)[g, :, s]  # [n, T]
-        return zs.contiguous(), ys.contiguous()
+        (tiled_rows).  It reads ``y`` through the public name, as any caller from outside
+        does, so the label bits turn invalid; the batch's own methods gather from the private
+        tensor (tiled_rows(self.z, self._y, ...)) and keep them."""
+        return tiled_rows(self.z, self.y, self.L, seqs)
 
     def generate_simulate(self, base_seed: int = 0, run0: int = 0, nbatch: int = 1,
                           eta0: float = SQRT2, gmax=None, pipelined: bool = True,
@@ -1766,8 +1821,12 @@ class DeviceBatch:
         flags = 0 if pipelined else _lib.OCX_GENSIM_SEQUENTIAL
         if self.exact:
             flags |= _lib.OCX_GENSIM_TWO_PASS
+        if nbatch > 0:
+            # each batch is read once, by FTRL kernels that keep y's doubles beside the
+            # generator: the tile is not written, so it no longer describes y
+            self._bits_state = "invalid"
         self._call("ocx_dev_gen_simulate", self._lp(), int(base_seed), int(run0), int(nbatch),
-                  self.z.data_ptr(), self.y.data_ptr(), float(eta0), self.regret.data_ptr(),
+                  self.z.data_ptr(), self._y.data_ptr(), float(eta0), self.regret.data_ptr(),
                   gmax.data_ptr() if gmax is not None else None, flags, int(sub_seqs), self._sp)
         self.rows_clipped = True
         return self.regret
