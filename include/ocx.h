@@ -73,7 +73,8 @@
  * regret-grid symbols (ocx_ftrl_exact_grid_group, ocx_ftrl_exact_grid_workspace_bytes,
  * ocx_dev_ftrl_vs_exact_curve_etas, ocx_ftrl_vs_exact_curve_etas_batch), and for the label-bit
  * symbols (ocx_label_bits_words, ocx_dev_pack_bits, ocx_dev_gen_gT_bits,
- * ocx_dev_simulate_alg_bits).
+ * ocx_dev_simulate_alg_bits), and for the anytime-regret symbol
+ * (ocx_dev_simulate_alg_anytime).
  *
  * Checking the ABI: one intermediate 0.1.x tree exported ocx_ftrl_vs_exact_batch WITH a
  * `norm` argument under the same symbol and the same version number as the release without
@@ -474,6 +475,33 @@ int ocx_simulate_alg_curve_batch(const double* z, const double* y, int64_t B, in
                                  int alg_flag, double eta0, const int64_t* checkpoints, int64_t K,
                                  double* regret, double* cum_loss, double* comp_loss,
                                  int32_t* closed_out, int lanes_per_seq, int device);
+
+/* Anytime regret: the running max of the regret over EVERY prefix, in one pass and without a
+ * workspace.  With R_t = regret of simulate_alg on (z[b][:t], y[b][:t], alg_flag, eta0) in its
+ * closed form cum_t - (t/2 - ||theta_t||) (column t of ocx_dev_simulate_alg_curve with the
+ * closed-form flag, bit for bit in the same layout), for t = 1 .. T:
+ *   open_from[b]  the first t whose prefix the kernel could not certify (rows in the unit ball,
+ *                 labels +-1, sub-gradients -y/2: ocx_dev_simulate_alg_ex's certificate);
+ *                 T + 1 if every prefix is certified.  Nothing from open_from[b] on enters the
+ *                 other outputs: the caller completes those prefixes with the curve entry
+ *   sup[b][k]     max of R_t over 1 <= t <= min(t_k, open_from[b] - 1); -inf if that is empty
+ *   argsup[b][k]  the smallest t attaining sup[b][k]; 0 with -inf
+ *   trace_tiled   R_t of sequence b = g * S + s at [(g * T + (t - 1)) * S + s] (y_tiled's
+ *                 layout, L->y_elems doubles); NaN from open_from[b] on
+ * device: checkpoints is a DEVICE int64 array [K], strictly increasing in [1, L->T] — a
+ * precondition the call cannot see (K <= T it can): an array that breaks it gives meaningless
+ * numbers, but the kernel never leaves the batch and the outputs whatever it holds;
+ * sup [B][K] double, argsup [B][K] int64, open_from [B] int64, trace_tiled: each nullable;
+ * padding sequences' trace slots are not written;
+ * flags: must contain OCX_ALG_CLOSED_COMPARATOR / OCX_ALG_CLIPPED_ROWS (one request): without
+ * the closed form the statistic has no one-pass form, and the call returns OCX_E_INVALID;
+ * K == 0 without a trace, B == 0 and T == 0 are valid and launch nothing;
+ * asynchronous, no allocation, no sync, no workspace: capture-safe like the other dev entry
+ * points.  Cost: one read of z, plus one norm of theta per step. */
+int ocx_dev_simulate_alg_anytime(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                                 int alg_flag, double eta0, const int64_t* checkpoints, int64_t K,
+                                 double* sup, int64_t* argsup, int64_t* open_from,
+                                 double* trace_tiled, int flags, void* stream);
 
 /* Step-size sweeps: FTRL (fast_algorithms.py:88-115, alg_flag 0) for M values of eta0 in
  * passes over z that each serve a group of them.  For every m,

@@ -22,7 +22,7 @@ BUILD = os.path.join(ROOT, "build", "ocx")
 LIB = os.path.join(PKG, "libocx.so")
 ARCH = os.environ.get("OCX_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["ocx_sim.hip", "ocx_alg_curve.hip", "ocx_alg_etas.hip", "ocx_alg_curve_etas.hip", "ocx_alg_pipe.hip", "ocx_smart_wave.hip", "ocx_smart_wave_cols.hip", "ocx_smart_thresholds.hip", "ocx_smart_curve.hip", "ocx_smart_grid.hip", "ocx_smart_wave_grid.hip", "ocx_ftrl_exact.hip", "ocx_ftrl_exact_curve.hip", "ocx_ftrl_exact_grid.hip", "ocx_gen.hip",
+SOURCES = ["ocx_sim.hip", "ocx_alg_curve.hip", "ocx_alg_anytime.hip", "ocx_alg_etas.hip", "ocx_alg_curve_etas.hip", "ocx_alg_pipe.hip", "ocx_smart_wave.hip", "ocx_smart_wave_cols.hip", "ocx_smart_thresholds.hip", "ocx_smart_curve.hip", "ocx_smart_grid.hip", "ocx_smart_wave_grid.hip", "ocx_ftrl_exact.hip", "ocx_ftrl_exact_curve.hip", "ocx_ftrl_exact_grid.hip", "ocx_gen.hip",
            "ocx_gen_wave.hip", "ocx_stream.hip", "ocx_twin32.hip", "ocx_twin32_cols.hip", "ocx_comp_blas.hip",
            "ocx_exact_ball.hip", "ocx_exact_wide.hip", "ocx_exact_big.hip", "ocx_pipeline.hip", "ocx_capi.hip"]
 HEADERS = ["../../include/ocx_testing.h", "ocx_internal.h", "ocx_rng.h", "ocx_sim_kernels.h", "zig_tables.h",

@@ -105,6 +105,8 @@ SIGNATURES = {
     "ocx_simulate_alg_curve_batch": (c_int, [c_dp, c_dp, c_i64, c_i64, c_i64, c_int, c_double,
                                              c_i64p, c_i64, c_dp, c_dp, c_dp,
                                              ctypes.POINTER(ctypes.c_int32), c_int, c_int]),
+    "ocx_dev_simulate_alg_anytime": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_int, c_double,
+                                             c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp]),
     "ocx_etas_group": (c_int, [ctypes.POINTER(Layout), c_i64]),
     "ocx_dev_simulate_alg_etas": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_dp, c_i64, c_vp,
                                           c_vp, c_vp, c_vp, c_int, c_vp]),

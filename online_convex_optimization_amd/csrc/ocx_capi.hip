@@ -459,6 +459,31 @@ int ocx_dev_simulate_alg_curve(const ocx_layout* L, const double* z_tiled, const
     return OCX_OK;
 }
 
+int ocx_dev_simulate_alg_anytime(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
+                                 int alg_flag, double eta0, const int64_t* checkpoints, int64_t K,
+                                 double* sup, int64_t* argsup, int64_t* open_from,
+                                 double* trace_tiled, int flags, void* stream) {
+    StreamDevice sd_(stream);
+    if (int rc = check_layout(L)) return rc;
+    if (L->B < 0 || L->T < 0 || L->G != ceil_div(L->B, L->S))
+        return fail(OCX_E_INVALID, "corrupt layout");
+    if (flags & ~(OCX_ALG_CLIPPED_ROWS | OCX_ALG_CLOSED_COMPARATOR))
+        return fail(OCX_E_INVALID, "unknown flags");
+    if (!(flags & (OCX_ALG_CLIPPED_ROWS | OCX_ALG_CLOSED_COMPARATOR)))
+        return fail(OCX_E_INVALID,
+                    "anytime regret needs OCX_ALG_CLOSED_COMPARATOR: without the closed form it "
+                    "has no one-pass form");
+    if (K < 0) return fail(OCX_E_INVALID, "K < 0");
+    // strictly increasing checkpoints in [1, T]: at most T of them
+    if (K > L->T) return fail(OCX_E_INVALID, "more checkpoints than horizons 1..T");
+    if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL input buffer");
+    if (K > 0 && !checkpoints) return fail(OCX_E_INVALID, "NULL checkpoints");
+    if ((K == 0 && !trace_tiled) || L->B == 0 || L->T == 0) return OCX_OK;
+    OCX_HIP(ocx_launch_alg_anytime(L, z_tiled, y_tiled, alg_flag != 0 ? 1 : 0, eta0, checkpoints, K,
+                                   sup, argsup, open_from, trace_tiled, 1, (hipStream_t)stream));
+    return OCX_OK;
+}
+
 // the smallest instantiated group that holds M step sizes, capped at `best`
 static int etas_group_for(const ocx_layout* L, int64_t M, int best) {
     int g = best;

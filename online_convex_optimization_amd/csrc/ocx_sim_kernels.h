@@ -46,6 +46,16 @@ hipError_t ocx_launch_alg_curve(const ocx_layout* L, const double* zt, const dou
                                 double eta0, const int64_t* ck, int64_t K, double* reg,
                                 double* cum, double* comp, int* closed_out, int onepass,
                                 void* ws, hipStream_t st);
+// Anytime regret (ocx_alg_anytime.hip): the running max of the closed-form regret over every
+// prefix t = 1 … T, and the smallest t attaining it, emitted at the K checkpoints ck (device,
+// strictly increasing in [1, T]): sup / argsup [B][K]; open_from [B], the first t the kernel
+// could not certify (T + 1: none; nothing after it enters the max); trace, in y_tiled's layout,
+// the regret of every step (NaN where not certified).  Each output nullable.  One pass over z,
+// no workspace, the curve's dispatch (the pipelined loop where ocx_pipe_supported(L)).
+hipError_t ocx_launch_alg_anytime(const ocx_layout* L, const double* zt, const double* yt, int ftl,
+                                  double eta0, const int64_t* ck, int64_t K, double* sup,
+                                  int64_t* argsup, int64_t* open_from, double* trace, int onepass,
+                                  hipStream_t st);
 // Step-size sweeps (ocx_alg_etas.hip): FTRL for the M step sizes etas (HOST, read at call
 // time) in passes of at most `group` (1, 2 or 4; ocx_etas_instance) columns; outputs [B][M]
 // (each nullable).  The multi-η form of the pipelined kernel where ocx_pipe_supported(L), of

@@ -122,6 +122,81 @@ def simulate_alg_curve_batch(z, y, checkpoints, alg_flag: int = 0, eta0: float =
     return reg
 
 
+def _anytime_checkpoints(checkpoints, T: int) -> np.ndarray:
+    """The checkpoint horizons of an anytime regret: _checkpoints' rules inside [1, T] (a
+    prefix has at least one step); None: [T], or the empty list at T = 0."""
+    T = int(T)
+    if checkpoints is None:
+        checkpoints = [T] if T > 0 else []
+    ck = _checkpoints(checkpoints, T)
+    if ck.size and ck.min() < 1:
+        raise ValueError(f"anytime checkpoints must lie in [1, T = {T}], got {ck.min()}")
+    return ck
+
+
+def _anytime_fold(torch, reg, lo: int, open_from, ck: np.ndarray, sup, argsup, run_best, run_arg,
+                  trace=None):
+    """One chunk of simulate_alg_anytime's completion.  reg [B, n]: the curve's regret at the
+    horizons lo … lo + n - 1; open_from [B]; sup / argsup [B, K] at the horizons ck (host);
+    run_best / run_arg [B]: the running max and its first argmax over the horizons before lo
+    (of the sequences that are open by then; the others' never get out).  Only the open
+    entries (t >= open_from[b]) are folded in, a later t only where strictly greater; the
+    columns of the checkpoints inside the chunk, the open trace entries and the returned
+    running pair are updated.  Tensors on one device, which need not be a GPU."""
+    n = int(reg.shape[1])
+    dev = reg.device
+    ts = torch.arange(lo, lo + n, dtype=torch.int64, device=dev)
+    is_open = ts[None, :] >= open_from[:, None]
+    if trace is not None:
+        trace[:, lo - 1:lo - 1 + n] = torch.where(is_open, reg, trace[:, lo - 1:lo - 1 + n])
+    vals = torch.where(is_open, reg, torch.full_like(reg, -math.inf))
+    cm = torch.maximum(torch.cummax(vals, dim=1).values, run_best[:, None])
+    prev = torch.cat([run_best[:, None], cm[:, :-1]], dim=1)
+    # the horizons that set a new record; the latest of them so far is the first argmax
+    rec = torch.where(vals > prev, ts[None, :].expand_as(vals),
+                      torch.zeros_like(vals, dtype=torch.int64))
+    am = torch.maximum(torch.cummax(rec, dim=1).values, run_arg[:, None])
+    ks = np.nonzero((ck >= lo) & (ck < lo + n))[0]
+    if ks.size:
+        kd = torch.as_tensor(ks).to(dev)
+        col = torch.as_tensor(ck[ks] - lo).to(dev)
+        upd = open_from[:, None] <= torch.as_tensor(ck[ks]).to(dev)[None, :]
+        sup[:, kd] = torch.where(upd, cm[:, col], sup[:, kd])
+        argsup[:, kd] = torch.where(upd, am[:, col], argsup[:, kd])
+    return cm[:, -1].clone(), am[:, -1].clone()
+
+
+def simulate_alg_anytime_batch(z, y, checkpoints=None, alg_flag: int = 0, eta0: float = SQRT2, *,
+                               lanes_per_seq: int = LANES_BEST, device: int = 0,
+                               return_trace: bool = False):
+    """Anytime regret of B host sequences (DeviceBatch.simulate_alg_anytime on a packed
+    batch): a dict of numpy arrays ``sup`` [B, K] (max over t <= t_k of the regret of
+    simulate_alg on (z[b, :t], y[b, :t])), ``argsup`` [B, K] int64 (the smallest such t),
+    ``open_from`` [B] int64 and, with ``return_trace``, ``trace`` [B, T] (the regret of every
+    prefix).  ``checkpoints`` defaults to [T].
+
+    Bit-exact layouts (lanes_per_seq 1 / -k) take ``closed_comparator=False``, as
+    simulate_alg_curve_batch does: every prefix streams the reference's comparator sum,
+    O(T²) rows per sequence.  The other layouts take the closed form in one pass wherever the
+    kernel certifies the prefix and complete the rest from the curve."""
+    z = _f64(z)
+    y = _f64(y)
+    B, T, d = _check_zy(z, y)
+    ck = _anytime_checkpoints(checkpoints, T)
+    K = int(ck.size)
+    if B == 0 or T == 0 or (K == 0 and not return_trace):  # nothing to compute: no device
+        out = {"sup": np.full((B, K), -np.inf), "argsup": np.zeros((B, K), dtype=np.int64),
+               "open_from": np.full((B,), T + 1, dtype=np.int64)}
+        if return_trace:
+            out["trace"] = np.zeros((B, T))
+        return out
+    db = DeviceBatch(B, T, d, lanes_per_seq=lanes_per_seq, device=int(device))
+    db.pack(z, y)
+    res = db.simulate_alg_anytime(ck, alg_flag, eta0, trace=return_trace)
+    with db._on_stream():
+        return {k: v.cpu().numpy() for k, v in res.items()}
+
+
 def _etas(etas) -> np.ndarray:
     """The step sizes of a sweep as a contiguous float64 array: a one-dimensional list of real
     numbers (any values, any order, duplicates allowed).  Raises ValueError otherwise."""
@@ -1102,6 +1177,89 @@ class DeviceBatch:
         self._keep_curve = self._hold(ckd, ws)
         return out
 
+    def simulate_alg_anytime(self, checkpoints=None, alg_flag: int = 0, eta0: float = SQRT2,
+                             closed_comparator: Optional[bool] = None, trace: bool = False):
+        """Anytime regret of the resident batch: the running max of FTRL / FTL's regret over
+        EVERY prefix.  With R_t column t of ``simulate_alg_curve(range(1, T + 1), alg_flag, eta0,
+        closed_comparator)``, returns device tensors
+
+          ``sup``       [B, K] float64: max of R_t over t = 1 … t_k,
+          ``argsup``    [B, K] int64: the smallest t attaining it,
+          ``open_from`` [B] int64: the first t whose prefix the kernel could not certify
+                        (T + 1: none),
+          ``trace``     [B, T] float64, R_1 … R_T (only with ``trace=True``),
+
+        for the horizons t_k of ``checkpoints`` (default ``[T]``; strictly increasing integers
+        in [1, T], validated here; T = 0 allows only an empty list).  ``closed_comparator``
+        defaults as in simulate_alg_curve.
+
+        Cost.  With the closed form (ocx_dev_simulate_alg_anytime) the certified prefixes take
+        ONE pass over z, no workspace, one extra norm of theta per step: O(T) per sequence.
+        The prefixes the kernel cannot certify (t >= open_from: exact ties on the deterministic
+        families, edited rows) are completed by simulate_alg_curve on this same batch — the
+        same layout, hence the same bits — at every horizon from min(open_from) to the last
+        one asked for, in chunks whose curve workspace stays under 1 GiB; each uncertified
+        (sequence, t) pair streams its prefix, O(T²) rows per open sequence.  Only the open
+        (sequence, t) entries are folded in; on equal values the earlier t wins.
+        ``closed_comparator=False`` produces the whole result this way without the new kernel:
+        the bit-exact mode, O(T²) for every sequence (open_from is then 1 throughout).
+        Synchronises once (open_from is read to decide on the completion).  With K = 0 and no
+        trace nothing runs and open_from stays T + 1."""
+        torch = self.torch
+        T, B = int(self.L.T), int(self.L.B)
+        ck = _anytime_checkpoints(checkpoints, T)
+        K = int(ck.size)
+        if closed_comparator is None:
+            closed_comparator = not self.exact
+        closed_comparator = bool(closed_comparator)
+        G, S = int(self.L.G), int(self.L.S)
+        with torch.cuda.device(self.device), self._on_stream():
+            ckd = torch.as_tensor(ck).to(self.device)
+            sup = torch.full((B, K), -math.inf, dtype=torch.float64, device=self.device)
+            argsup = torch.zeros((B, K), dtype=torch.int64, device=self.device)
+            open_from = torch.full((B,), T + 1 if closed_comparator else 1, dtype=torch.int64,
+                                   device=self.device)
+            tt = (torch.full((max(int(self.L.y_elems), 1),), math.nan, dtype=torch.float64,
+                             device=self.device) if trace else None)
+        out = {"sup": sup, "argsup": argsup, "open_from": open_from}
+        if B == 0 or T == 0 or (K == 0 and not trace):
+            if trace:
+                out["trace"] = torch.zeros((B, T), dtype=torch.float64, device=self.device)
+            return out
+        if closed_comparator:
+            self._call("ocx_dev_simulate_alg_anytime", self._lp(), self.z.data_ptr(),
+                       self._y.data_ptr(), int(alg_flag), float(eta0),
+                       ckd.data_ptr() if K else None, K, sup.data_ptr(), argsup.data_ptr(),
+                       open_from.data_ptr(), tt.data_ptr() if trace else None,
+                       _lib.OCX_ALG_CLIPPED_ROWS, self._sp)
+            self._keep_anytime = self._hold(ckd, tt)
+        with torch.cuda.device(self.device), self._on_stream():
+            tr = None
+            if trace:  # [G, T, S] -> [G·S, T][:B]: views and one copy, no kernel of ours
+                tr = tt[:G * T * S].view(G, T, S).permute(0, 2, 1).reshape(G * S, T)[:B].contiguous()
+                out["trace"] = tr
+            lo0 = int(open_from.min().item())
+        hi0 = T if trace else int(ck[-1])
+        if lo0 > hi0:
+            return out
+        # completion of the open prefixes from the dense curve, a chunk of horizons at a time
+        per_ck = max(int(_lib.load().ocx_curve_workspace_bytes(self._lp(), 1)), 1)
+        chunk = max(1, (1 << 30) // per_ck)
+        with torch.cuda.device(self.device), self._on_stream():
+            if K:  # the max over the certified prefix of every sequence that is completed
+                run_best, run_arg = sup[:, K - 1].clone(), argsup[:, K - 1].clone()
+            else:
+                run_best = torch.full((B,), -math.inf, dtype=torch.float64, device=self.device)
+                run_arg = torch.zeros((B,), dtype=torch.int64, device=self.device)
+        for lo in range(lo0, hi0 + 1, chunk):
+            hi = min(lo + chunk - 1, hi0)
+            reg = self.simulate_alg_curve(np.arange(lo, hi + 1, dtype=np.int64), alg_flag, eta0,
+                                          closed_comparator)["regret"]
+            with torch.cuda.device(self.device), self._on_stream():
+                run_best, run_arg = _anytime_fold(torch, reg, lo, open_from, ck, sup, argsup,
+                                                  run_best, run_arg, tr)
+        return out
+
     def simulate_alg_etas(self, etas, closed_comparator: Optional[bool] = None, *, _group=None):
         """Step-size sweep of the resident batch (ocx_dev_simulate_alg_etas, async): FTRL for
         every eta0 of ``etas`` (a one-dimensional list of real numbers, validated here), each
@@ -1904,6 +2062,102 @@ def gT_regret_curves(T: int, runs: int, checkpoints, *, base_seed: int = 0, d: i
             out = reg.cpu().numpy()
             cl = closed.cpu().numpy() if closed is not None else None
     return (out, cl) if return_closed else out
+
+
+def _gT_anytime_batches(T, runs, ck, base_seed, d, eta0, run0, lanes_per_seq, device, batch, each):
+    """The batch loop of gT_anytime and gT_anytime_max: every batch of the g(T) sampler's
+    sequences generated on device and observed at every step (simulate_alg_anytime);
+    ``each(db, r0, n, res)`` receives the batch's device results.  ``batch`` None: as many
+    sequences as keep z and y under GT_CURVE_HBM_BUDGET bytes (the anytime kernel has no
+    workspace).  Returns the last DeviceBatch (its stream orders the results)."""
+    release_buffers(device)
+    if batch is None:
+        L = _lib.layout(runs, T, d, lanes_per_seq)  # bytes per wave-group of S sequences
+        per_group = 8 * (L.z_elems + L.y_elems) // L.G
+        batch = max(1, GT_CURVE_HBM_BUDGET // max(per_group, 1)) * L.S
+    batch = min(int(batch), runs)
+    db = None
+    for r0 in range(0, runs, batch):
+        n = min(batch, runs - r0)
+        if db is None or db.L.B != n:
+            db = None  # the short last batch: free the full one first
+            db = DeviceBatch(n, T, d, lanes_per_seq=lanes_per_seq, device=int(device))
+        db.generate_gT(base_seed, int(run0) + r0)
+        each(db, r0, n, db.simulate_alg_anytime(ck, 0, eta0))
+    return db
+
+
+def _gT_anytime_args(T, runs, checkpoints, base_seed, batch):
+    if base_seed < 0 or base_seed >= 2 ** 64:
+        raise ValueError("base_seed must be in [0, 2**64)")
+    T, runs = int(T), int(runs)
+    if runs < 0:
+        raise ValueError("runs must be >= 0")
+    ck = _anytime_checkpoints(checkpoints, T)
+    if batch is not None and int(batch) < 1:
+        raise ValueError("batch must be >= 1")
+    return T, runs, ck
+
+
+def gT_anytime(T: int, runs: int, checkpoints=None, *, base_seed: int = 0, d: int = 5,
+               eta0: float = SQRT2, run0: int = 0, lanes_per_seq: int = LANES_BEST,
+               device: int = 0, batch: Optional[int] = None):
+    """FTRL's anytime regret on the g(T) sampler: for the sequences _rng(base_seed, T, run),
+    run in [run0, run0 + runs) (the rows gT_regret_curves observes), ``sup`` [runs, K] — the
+    largest regret any prefix of at most t_k steps reached — and ``argsup`` [runs, K] int64, the
+    first step at which it was reached.  ``checkpoints`` defaults to [T].  sup[:, k] bounds
+    gT_regret_curves(...)[:, k] from above and is non-decreasing in k.
+
+    Generated on device and observed at every step in one pass (simulate_alg_anytime), in
+    batches of ``batch`` sequences — by default as many as keep z and y under
+    GT_CURVE_HBM_BUDGET bytes; a short last batch is handled.  Only the two [runs, K] results
+    cross PCIe."""
+    import torch
+    T, runs, ck = _gT_anytime_args(T, runs, checkpoints, base_seed, batch)
+    K = int(ck.size)
+    if runs == 0 or K == 0:
+        return np.zeros((runs, K)), np.zeros((runs, K), dtype=np.int64)
+    dev = torch.device("cuda", int(device))
+    with torch.cuda.device(dev):
+        sup = torch.empty((runs, K), dtype=torch.float64, device=dev)
+        arg = torch.empty((runs, K), dtype=torch.int64, device=dev)
+
+        def each(db, r0, n, res):
+            with db._on_stream():
+                sup[r0:r0 + n].copy_(res["sup"])
+                arg[r0:r0 + n].copy_(res["argsup"])
+
+        db = _gT_anytime_batches(T, runs, ck, base_seed, d, eta0, run0, lanes_per_seq, device,
+                                 batch, each)
+        with db._on_stream():
+            return sup.cpu().numpy(), arg.cpu().numpy()
+
+
+def gT_anytime_max(T: int, runs: int, checkpoints=None, *, base_seed: int = 0, d: int = 5,
+                   eta0: float = SQRT2, run0: int = 0, lanes_per_seq: int = LANES_BEST,
+                   device: int = 0, batch: Optional[int] = None):
+    """g[K] = max(0, max over runs of gT_anytime(...)[0][:, k]): the anytime envelope of g(T) —
+    the largest regret FTRL reached at ANY step t <= t_k over the g(T) sampler's runs —
+    reduced on device batch by batch (ocx_dev_max_regret_cols); only K doubles cross PCIe.
+    Non-decreasing in k, and >= the checkpoint envelope gT_surface reads at the same t_k."""
+    import torch
+    T, runs, ck = _gT_anytime_args(T, runs, checkpoints, base_seed, batch)
+    K = int(ck.size)
+    if runs == 0 or K == 0:
+        return np.zeros(K)
+    dev = torch.device("cuda", int(device))
+    with torch.cuda.device(dev):
+        g = torch.zeros(K, dtype=torch.float64, device=dev)
+
+        def each(db, r0, n, res):
+            db._call("ocx_dev_max_regret_cols", res["sup"].data_ptr(), n, K, g.data_ptr(),
+                     1 if r0 else 0, db._sp)
+            db._hold(res["sup"], g)
+
+        db = _gT_anytime_batches(T, runs, ck, base_seed, d, eta0, run0, lanes_per_seq, device,
+                                 batch, each)
+        with db._on_stream():
+            return g.cpu().numpy()
 
 
 def gT_regrets_etas(T: int, runs: int, etas, *, base_seed: int = 0, d: int = 5, run0: int = 0,
