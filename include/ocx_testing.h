@@ -49,6 +49,30 @@ int ocx_test_alg_range(const ocx_layout* L, const double* z_tiled, const double*
                        double eta0, int onepass, int64_t g0, int64_t gn, double* regret,
                        double* gmax, void* stream);
 
+/* One launch of the overlapped pipeline's sub-batch generator over sequences
+ * [b_off, b_off + nseq) of the layout: the g(T) sampler's streams _rng(base_seed, T, run0 + b)
+ * written into the full batch's tiles (y_bits nullable), every slot outside the range left
+ * alone.  form 3: the range launcher at three waves per SIMD (its 128-VGPR instance); form 4:
+ * at four (its 96-VGPR instance); form 6: the few-stream range launcher (d = 64 only).  The
+ * range must lie inside the G * S sequence slots of the layout (else OCX_E_INVALID, checked
+ * here); what the launcher itself rejects — b_off or nseq not a multiple of 4, a layout other
+ * than d = 16 / 32 / 64 with P * C = d — comes back as OCX_E_INVALID with nothing launched.
+ * Synchronises `stream`. */
+int ocx_test_gen_gT_range(const ocx_layout* L, uint64_t base_seed, int64_t run0, int64_t b_off,
+                          int64_t nseq, int form, double* z_tiled, double* y_tiled,
+                          uint64_t* y_bits, void* stream);
+
+/* One launch of the trailing pipeline's row-range generator: rows [t_off, t_off + nrows) of
+ * every sequence of the layout's full-horizon tile, the streams fresh (st_in NULL) or resumed
+ * from st_in, the stream after the rows saved to st_out (nullable; a buffer other than st_in).
+ * st_in / st_out: caller-owned device buffers of 6 * G * S 64-bit words.  labels = 1: the launch
+ * also draws the T labels that follow the sequence's last normal (only meaningful on the range
+ * that ends at T); labels = 0 leaves y_tiled alone.  Any layout; any cut points.  A range
+ * outside [0, T] is OCX_E_INVALID with nothing launched.  Synchronises `stream`. */
+int ocx_test_gen_gT_rows(const ocx_layout* L, uint64_t base_seed, int64_t run0, int64_t t_off,
+                         int64_t nrows, const uint64_t* st_in, uint64_t* st_out, int labels,
+                         double* z_tiled, double* y_tiled, void* stream);
+
 /* The pipelined FTRL (ftl = 0) / FTL (ftl = 1) kernel's persistent instance — the one a batch
  * of more wave-groups than are resident at once launches, each wave looping over groups w,
  * w + nwaves, ... — on a resident batch of any size, with the number of waves forced to

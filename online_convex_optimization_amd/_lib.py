@@ -189,6 +189,10 @@ TEST_SIGNATURES = {
                                           c_vp, c_vp, c_vp]),
     "ocx_test_alg_range": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_double, c_int, c_i64,
                                    c_i64, c_vp, c_vp, c_vp]),
+    "ocx_test_gen_gT_range": (c_int, [ctypes.POINTER(Layout), c_u64, c_i64, c_i64, c_i64, c_int,
+                                      c_vp, c_vp, c_vp, c_vp]),
+    "ocx_test_gen_gT_rows": (c_int, [ctypes.POINTER(Layout), c_u64, c_i64, c_i64, c_i64, c_vp,
+                                     c_vp, c_int, c_vp, c_vp, c_vp]),
     "ocx_test_alg_pipe_persistent": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_int, c_double,
                                              c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "ocx_test_alg_pipe_persistent_bits": (c_int, [ctypes.POINTER(Layout), c_vp, c_vp, c_vp, c_int,

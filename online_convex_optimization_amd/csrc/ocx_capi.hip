@@ -2421,6 +2421,51 @@ int ocx_test_alg_range(const ocx_layout* L, const double* z_tiled, const double*
     return OCX_OK;
 }
 
+// a generator launcher's error as a status: a rejected argument is OCX_E_INVALID
+static int gen_launch_status(hipError_t e, hipError_t es, const char* what) {
+    if (e == hipErrorInvalidValue) return fail(OCX_E_INVALID, std::string(what) + ": rejected by the launcher");
+    if (e != hipSuccess) return fail(OCX_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    if (es != hipSuccess) return fail(OCX_E_HIP, std::string(what) + ": " + hipGetErrorString(es));
+    return OCX_OK;
+}
+
+int ocx_test_gen_gT_range(const ocx_layout* L, uint64_t base_seed, int64_t run0, int64_t b_off,
+                          int64_t nseq, int form, double* z_tiled, double* y_tiled,
+                          uint64_t* y_bits, void* stream) {
+    StreamDevice sd_(stream);
+    if (int rc = check_layout(L)) return rc;
+    if (run0 < 0) return fail(OCX_E_INVALID, "run0 < 0");
+    if (form != 3 && form != 4 && form != 6) return fail(OCX_E_INVALID, "form must be 3, 4 or 6");
+    if (L->B < 0 || L->T < 0 || L->G != ceil_div(L->B, L->S)) return fail(OCX_E_INVALID, "corrupt layout");
+    if (b_off < 0 || nseq < 0 || b_off + nseq > L->G * L->S)
+        return fail(OCX_E_INVALID, "sequence range outside the layout");
+    if (nseq > 0 && L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL buffer");
+    const hipStream_t st = (hipStream_t)stream;
+    const hipError_t e =
+        form == 6 ? ocx_launch_gen_gT_range_lr(L, base_seed, run0, b_off, nseq, z_tiled, y_tiled, st, y_bits)
+                  : ocx_launch_gen_gT_range(L, base_seed, run0, b_off, nseq, form, z_tiled, y_tiled, st,
+                                            y_bits);
+    const hipError_t es = hipStreamSynchronize(st);
+    return gen_launch_status(e, es, "ocx_launch_gen_gT_range");
+}
+
+int ocx_test_gen_gT_rows(const ocx_layout* L, uint64_t base_seed, int64_t run0, int64_t t_off,
+                         int64_t nrows, const uint64_t* st_in, uint64_t* st_out, int labels,
+                         double* z_tiled, double* y_tiled, void* stream) {
+    StreamDevice sd_(stream);
+    if (int rc = check_layout(L)) return rc;
+    if (run0 < 0) return fail(OCX_E_INVALID, "run0 < 0");
+    if (labels != 0 && labels != 1) return fail(OCX_E_INVALID, "labels must be 0 or 1");
+    if (L->B < 0 || L->T < 0 || L->G != ceil_div(L->B, L->S)) return fail(OCX_E_INVALID, "corrupt layout");
+    if (st_out && st_out == st_in) return fail(OCX_E_INVALID, "st_out must be a buffer other than st_in");
+    if (L->z_elems && (!z_tiled || !y_tiled)) return fail(OCX_E_INVALID, "NULL buffer");
+    const hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = ocx_launch_gen_gT_rows(L, base_seed, run0, t_off, nrows, st_in, st_out,
+                                                labels, z_tiled, y_tiled, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    return gen_launch_status(e, es, "ocx_launch_gen_gT_rows");
+}
+
 int ocx_test_alg_pipe_persistent(const ocx_layout* L, const double* z_tiled, const double* y_tiled,
                                  int ftl, double eta0, int onepass, int64_t nwaves, double* regret,
                                  double* cum, double* comp, int32_t* closed_out, void* stream) {
